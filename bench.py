@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- body-pair interactions/s of the brute-force N-body step (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, K timed steps, the JSON line (metric, value,
+unit, ms_per_step, the roofline of the kernel times taken inside the timed steps).  `--dump-outputs DIR` also writes the state the
+last timed step left (what a caller of the step reads back) as DIR/<name>.npy.  `--full` adds everything that takes runs of its
+own: the CPU baseline, the steady-state loop, the general-masses run, the rocprofv3 counter passes, the self-check of a multi-GPU
+run, the per-kernel pass of a Barnes-Hut run and the companion configs.
 
 One "step" = one nb_step_brute_force (rs-src/nbody.rs:106-162): all-pairs force + kick-drift over
 the whole synthetic system.  Workload: N = 262 144-body Plummer sphere (3-D float4 kernel,
@@ -46,10 +52,32 @@ KERNEL_NAMES = {1: "k_force_tile_pk", 6: "k_force_smem_pkw<unit_mass=0>", 7: "k_
                 -1: "k_force_strict", -8: "k_force_strict_pc<8,8>", -16: "k_force_strict_pc<16,4>"}
 
 
+def _use_built(module, so):
+    """A benchmark run measures the library that build() left and compiles nothing: a compile at the first step would count against
+    the run, and whoever benchmarks may only be allowed to read the tree. So the module's own build step, which takes a lock file
+    beside the library, is left out when the library is there. Where it is missing that step runs, and fails, as before."""
+    if os.path.exists(so):
+        module.build = lambda force=False: so
+
+
+def load_product():
+    import rust_exp_amd as rx
+
+    _use_built(rx.engine, rx.lib_path())
+    return rx
+
+
+def load_oracle():
+    from oracle import binding as ob
+
+    _use_built(ob, ob._SO)
+    return ob
+
+
 def cpu_baseline(st, seconds):
     """Oracle (CPU restatement of nbody.rs:132-144) on the host cores: a bounded i-slice of the same
     workload (work per target is uniform), threads = all cores with the reference's slab split."""
-    from oracle import binding as ob
+    ob = load_oracle()
 
     n = len(st["px"])
     cores = effective_cores()
@@ -77,7 +105,7 @@ def cpu_baseline(st, seconds):
 def cpu_baseline_barnes_hut(st, theta, dt, threads, reps):
     """The CPU-baseline leg of the Barnes-Hut measurements: the oracle's nb_step_barnes_hut
     (nbody.rs:186-480: serial tree build + `threads` traversal workers) timed on the host cores. Median ms per step."""
-    from oracle import binding as ob
+    ob = load_oracle()
 
     p = ob.particles(st["px"], st["py"], st["vx"], st["vy"], st["m"])
     ts, rc = [], 0
@@ -92,7 +120,7 @@ def bh_accuracy(st, theta, engine, threads):
     against the oracle's own f32 traversal (orc_bh_forces, nbody.rs:333-377) -- errors relative to max|F|, over ALL bodies.
     DESIGN.md section 4 allows the exact-sum tree class (device tree above 65 536 bodies) 0.1 % of bodies on a flipped opening
     decision, bounded by 2e-3: here that allowance is a measured figure of this run."""
-    from oracle import binding as ob
+    ob = load_oracle()
 
     n = len(st["px"])
     p = ob.particles(st["px"], st["py"], st["vx"], st["vy"], st["m"])
@@ -132,7 +160,7 @@ def reference_scene_line(no_cpu_baseline=False, frames=90):
     leg): BASELINE.md section 3 row CB -- the oracle's nb_step_barnes_hut on the same seeded scene, 1 thread, median of 30 -- and
     the force error of an engine in the level-1 configuration against the oracle's own traversal (orc_bh_forces, nbody.rs:333-377)."""
     os.environ.setdefault("NB_SEED", "1")
-    import rust_exp_amd as rx
+    rx = load_product()
 
     theta, dt, nthreads, n = 0.85, 0.01, 1, 10000
     rx.nb_stable_orbits(n, 0.5, 30.0)
@@ -164,7 +192,7 @@ def reference_scene_line(no_cpu_baseline=False, frames=90):
                       "tree": tree, "how": "RustNBodyExperiment.hs:42-65: timeIt around the FFI call, nb_draw 512x512 between calls, median of 30"},
            "bh_fallbacks": e.get_stat(rx.engine.NBX_STAT_BH_FALLBACKS)}
     if not no_cpu_baseline:
-        from oracle import binding as ob
+        ob = load_oracle()
 
         p = ob.particles(st["px"], st["py"], st["vx"], st["vy"], st["m"])
         q = p.copy()
@@ -252,7 +280,7 @@ def run_companions(base_argv=(), timeout=150):
         t0 = time.perf_counter()
         row = {"config": what, "argv": " ".join(argv)}
         try:
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-companions"] + list(base_argv) + argv,
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-companions"] + list(base_argv) + argv,
                                stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, env=dict(os.environ))
             lines = [ln for ln in r.stdout.decode(errors="replace").splitlines() if ln.startswith("{")]
             if r.returncode != 0 or not lines:
@@ -328,8 +356,39 @@ def parse_args():
                     help="skip the companions block (BASELINE configs #2, #4, #5 as short child runs after the official window)")
     ap.add_argument("--no-accuracy", action="store_true",
                     help="--workload bh: skip the full-size force-error check against the oracle's fp64 arbiter (cpu_baseline leg)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: CPU baseline, steady-state loop, general-masses run, rocprofv3 counter "
+                         "passes, the self-check of a multi-GPU run, the per-kernel pass of --workload bh, the companions block "
+                         "(each still has its --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: the state the last timed step left, as DIR/<name>.npy (float32)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000   # of array data: with the .npy headers the files stay under 64 MB in all
+
+
+def dump_outputs(directory, host):
+    """--dump-outputs: what the timed path computed in its last step, i.e. the arrays a caller reads back after it (positions,
+    velocities, masses), one DIR/<name>.npy each. Beyond DUMP_LIMIT_BYTES in all: the same seeded sample of bodies from every array.
+    Every rank calls this (the torch host's get_state is a collective); rank 0 writes."""
+    host.sync(); host.barrier()
+    st = host.get_state()
+    if host.rank != 0:
+        return
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in st.items()}
+    n = len(next(iter(arrays.values())))
+    keep = DUMP_LIMIT_BYTES // (4 * len(arrays))
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(n, keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
 
 
 def make_state(args, rx):
@@ -511,7 +570,7 @@ def run(real_stdout):
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     args = parse_args()
     if args.workload == "reference_scene":   # companion c0: its own line, nothing of the all-pairs machinery
-        os.write(real_stdout, (json.dumps(reference_scene_line(args.no_cpu_baseline)) + "\n").encode())
+        os.write(real_stdout, (json.dumps(reference_scene_line(args.no_cpu_baseline or not args.full)) + "\n").encode())
         return
     if args.n <= 0:
         args.n = 1048576 if args.workload == "bh" else 262144
@@ -529,7 +588,7 @@ def run(real_stdout):
 
     if host_kind == "torch":
         import torch  # noqa: F401  (before the HIP library: both then share torch's HIP runtime, see sharded.py)
-    import rust_exp_amd as rx
+    rx = load_product()
 
     n = args.n
     stage("initial conditions", host=host_kind, gpus=args.gpus, bodies=n, workload=args.workload)
@@ -586,8 +645,11 @@ def run(real_stdout):
     host.sync(); host.barrier()
     t1 = time.perf_counter()
     elapsed = host.reduce_max(t1 - t0)
+    if args.dump_outputs:
+        stage("dump outputs", ms_per_step=elapsed / args.steps * 1e3)
+        dump_outputs(args.dump_outputs, host)
     stage("per-rank kernel times", ms_per_step=elapsed / args.steps * 1e3)
-    if not profile_in_region:
+    if not profile_in_region and args.full:
         for e in host.engines:
             e.profile(True)
             e.profile_reset()
@@ -603,15 +665,15 @@ def run(real_stdout):
     engine = host.eng
     launch = engine.last_launch()   # of the timed loop (the blocks below launch other shapes)
     dev0 = getattr(host, "local_rank", 0)
-    do_verify = args.verify if args.verify is not None else (world > 1)
+    do_verify = args.verify if args.verify is not None else (args.full and world > 1)
     verify = None
     if do_verify and args.shard_of <= 1:
         verify = verify_against_plain_engine(host, args, rx, step, is_bh, dev0)
     steady = None
-    if host_kind == "single" and args.steady_seconds > 0 and args.shard_of <= 1:
+    if args.full and host_kind == "single" and args.steady_seconds > 0 and args.shard_of <= 1:
         steady = steady_state(host, step, args.steady_seconds)
     general = None
-    if (host_kind == "single" and not is_bh and args.shard_of <= 1 and not args.no_general_masses and args.mode == "fast"
+    if (args.full and host_kind == "single" and not is_bh and args.shard_of <= 1 and not args.no_general_masses and args.mode == "fast"
             and args.variant < 0 and args.source_bits == 32 and launch["variant"] == 7):
         # The same run on UNEQUAL masses (nb_random_disk's range, nbody.rs:62): positions unchanged, every body its own mass
         # -> no common mass -> the wave-split kernel WITH the per-interaction multiply by m_j (variant 6). What a caller
@@ -670,7 +732,7 @@ def run(real_stdout):
             # the per-split partial-acceleration slabs K1 writes for K2 are NOT algorithmic: they show up in `traffic`
             algorithmic = 16.0 * n + 16.0 * slab_rows
             traffic, traffic_info = None, None
-            if world == 1 and not args.no_traffic:
+            if args.full and world == 1 and not args.no_traffic:
                 tail = [a for a in sys.argv[1:] if a not in ("--no-cpu-baseline",)]
                 traffic_info = measure_traffic(tail + ["--no-cpu-baseline", "--no-traffic"], "k_force")
                 if traffic_info:
@@ -740,10 +802,24 @@ def run(real_stdout):
                 out["general_masses"] = general
         else:
             value = float(n) * args.steps / elapsed
+            walk_kind = engine.get_option(rx.engine.NBX_OPT_BH_WALK) if args.mode == "fast" else 0
+            out.update({
+                "metric": f"bodies/s through nb_step_barnes_hut (theta={args.theta}) at N={n}",
+                "value": value, "unit": "body-steps/s", "dtype": "f32",
+                "config": {"workload": f"plummer_disk_projection_N{n}_barnes_hut_theta{args.theta}_dt{DT}", "bodies": n,
+                           "seed": "0x5EED0001", "force_mode": args.mode, "host": host_kind, "sharding": sharding,
+                           "tree": {0: "host (reference-faithful insertion build)", 1: "device (bh_build.hip)"}[engine.get_stat(rx.engine.NBX_STAT_BH_LAST_TREE)],
+                           "walk": {0: "node by node (bh_eval.hip, rounds 1-3)", 1: "child groups, hand-scheduled loop (bh_walk.hip)",
+                                    2: "child groups, compiled loop (bh_walk.hip)"}[walk_kind]},
+                # steps of this run that the device tree was selected for but the host tree served (a refused build: EPS crowds,
+                # an exhausted pool, a warm sort whose buckets overflowed) -- each costs ~20 ms at a million bodies
+                "bh_fallbacks": engine.get_stat(rx.engine.NBX_STAT_BH_FALLBACKS),
+                "bh_last_refusal": "0x%x" % engine.get_stat(rx.engine.NBX_STAT_BH_REFUSAL),
+            })
+        if is_bh and args.full:   # the per-kernel split and the roofline come from the second pass of the steps and from counting passes
             ht = engine.bh_host_timing()
             wk = engine.bh_work_detail(args.theta)
             ev_s = max(per[0]["bh_eval_ms"], 1e-9) * 1e-3     # HIP events around the traversal: (tree -> child groups) + walk
-            walk_kind = engine.get_option(rx.engine.NBX_OPT_BH_WALK) if args.mode == "fast" else 0
             # the kernels of one traversal, by name: the walk, and (child-group walks) the conversion of the tree before it
             # (the wave form by its template brackets: "k_bh_walk_groups" alone also names k_bh_walk_groups_lane, the per-lane form --
             #  round 4's host-tree line averaged one such launch, 6 GB, into the traffic of the wave walk)
@@ -783,17 +859,6 @@ def run(real_stdout):
             groups_bytes = 80.0 * ht["nodes"]   # upper bound: an 80-byte record per node (interior ones have one), written once, read once
             algorithmic = 32.0 * ht["nodes"] + 24.0 * n + (2.0 * groups_bytes if walk_kind else 0.0)
             out.update({
-                "metric": f"bodies/s through nb_step_barnes_hut (theta={args.theta}) at N={n}",
-                "value": value, "unit": "body-steps/s", "dtype": "f32",
-                "config": {"workload": f"plummer_disk_projection_N{n}_barnes_hut_theta{args.theta}_dt{DT}", "bodies": n,
-                           "seed": "0x5EED0001", "force_mode": args.mode, "host": host_kind, "sharding": sharding,
-                           "tree": {0: "host (reference-faithful insertion build)", 1: "device (bh_build.hip)"}[engine.get_stat(rx.engine.NBX_STAT_BH_LAST_TREE)],
-                           "walk": {0: "node by node (bh_eval.hip, rounds 1-3)", 1: "child groups, hand-scheduled loop (bh_walk.hip)",
-                                    2: "child groups, compiled loop (bh_walk.hip)"}[walk_kind]},
-                # steps of this run that the device tree was selected for but the host tree served (a refused build: EPS crowds,
-                # an exhausted pool, a warm sort whose buckets overflowed) -- each costs ~20 ms at a million bodies
-                "bh_fallbacks": engine.get_stat(rx.engine.NBX_STAT_BH_FALLBACKS),
-                "bh_last_refusal": "0x%x" % engine.get_stat(rx.engine.NBX_STAT_BH_REFUSAL),
                 "ms_split": {"bh_eval_kernel": per[0]["bh_eval_ms"], "integrate_kernel": per[0]["integrate_ms"],
                              "host_download": ht["download_ms"],
                              # device tree: GPU time of the build, first launch to last (HIP events); host tree: host wall time
@@ -827,7 +892,7 @@ def run(real_stdout):
             out["steady_state"] = steady
         out.update({"device": info["name"], "arch": info["arch"], "compute_units": info["compute_units"],
                     "clock_khz": info["clock_khz"]})
-        if not args.no_cpu_baseline and world == 1 and args.shard_of <= 1:
+        if args.full and not args.no_cpu_baseline and world == 1 and args.shard_of <= 1:
             if is_bh:
                 cores = min(effective_cores(), 16)
                 ms1, rc = cpu_baseline_barnes_hut(st, args.theta, DT, cores, 3 if n > 200000 else 15)
@@ -845,7 +910,7 @@ def run(real_stdout):
                 out["cpu_baseline"] = cpu_baseline(st, args.cpu_seconds)
                 # the two rates are NOT the same work per interaction: say what each side computes
                 out["cpu_baseline"]["gpu_law"] = GPU_LAW_3D if out["config"]["launch"]["dim"] == 3 else GPU_LAW_2D
-        comp_ok = (host_kind == "single" and world == 1 and not is_bh and args.workload == "plummer" and n == 262144
+        comp_ok = (args.full and host_kind == "single" and world == 1 and not is_bh and args.workload == "plummer" and n == 262144
                    and args.mode == "fast" and args.variant < 0 and args.source_bits == 32 and args.shard_of <= 1
                    and args.jsplit == 0 and args.bpt == 0 and not args.no_companions)
         if comp_ok:

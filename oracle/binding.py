@@ -28,10 +28,16 @@ def build(force=False):
     import fcntl
 
     src = os.path.join(_HERE, "nbody_oracle.c")
+
+    def stale():
+        return not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src)
+
+    if not force and not stale():
+        return _SO   # nothing to do, nothing written: a user who may only read the tree can still load the library
     with open(os.path.join(_HERE, ".build.lock"), "w") as lock:   # several test processes may build at once
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
+            if force or stale():
                 subprocess.check_call(["make", "-C", _HERE, "-s"])
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)

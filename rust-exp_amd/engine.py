@@ -90,15 +90,20 @@ def build(force=False):
     Serialised with a file lock: the ranks of a multi-GPU launch may all get here at once."""
     import fcntl
 
+    srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if not f.startswith(".")] + [
+        os.path.join(_PKG, "..", "include", "nbody_mi355x.h")
+    ]
+
+    def stale():
+        return not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in srcs)
+
+    if not force and not stale():
+        return _SO   # nothing to do, nothing written: a user who may only read the tree can still load the library
     os.makedirs(os.path.join(_PKG, "lib"), exist_ok=True)
     with open(os.path.join(_PKG, "lib", ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if not f.startswith(".")] + [
-                os.path.join(_PKG, "..", "include", "nbody_mi355x.h")
-            ]
-            stale = not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in srcs)
-            if force or stale:
+            if force or stale():   # (again under the lock: another rank may have built it meanwhile)
                 have_hipcc = any(os.access(os.path.join(p, "hipcc"), os.X_OK)
                                  for p in os.environ.get("PATH", "").split(os.pathsep))
                 if not have_hipcc:

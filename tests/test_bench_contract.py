@@ -123,6 +123,43 @@ def test_companions_block_is_flat_scalars_and_survives_a_failed_child():
     assert all(v is None or isinstance(v, (int, float, str)) for v in f0.values())
 
 
+def test_dump_outputs_writes_every_array_and_samples_beyond_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 DIR/<name>.npy per array of the state the host returns; beyond the size limit the same seeded
+    sample of bodies from every array, identical from call to call; only rank 0 writes."""
+    class Host:
+        rank = 0
+
+        def __init__(self, n):
+            self.st = {k: np.arange(n, dtype=np.float32) + i for i, k in enumerate(("px", "py", "pz", "vx", "vy", "vz", "m"))}
+
+        def sync(self):
+            pass
+
+        barrier = sync
+
+        def get_state(self):
+            return self.st
+
+    assert bench.DUMP_LIMIT_BYTES <= 64 * 10**6
+    h = Host(1000)
+    bench.dump_outputs(str(tmp_path / "a"), h)
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in h.st)
+    for k, v in h.st.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, v)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 7 * 4 * 300)
+    bench.dump_outputs(str(tmp_path / "b"), h)
+    bench.dump_outputs(str(tmp_path / "c"), h)
+    px = np.load(tmp_path / "b" / "px.npy")
+    assert px.shape == (300,) and np.all(np.diff(px) > 0) and sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) < 7 * 4 * 300 + 7 * 200
+    for i, k in enumerate(h.st):
+        assert np.array_equal(np.load(tmp_path / "b" / (k + ".npy")), px + i)        # the same bodies in every array
+        assert np.array_equal(np.load(tmp_path / "c" / (k + ".npy")), px + i)        # ... and in every call
+    h.rank = 1
+    bench.dump_outputs(str(tmp_path / "d"), h)
+    assert not os.path.exists(tmp_path / "d")
+
+
 def test_cpu_baseline_says_who_ran_it_and_what_it_computes():
     """VERDICT r05 #4 / BASELINE.md section 3 ("state T and CPU model"): the cpu_baseline block names the CPU model, the share of
     the host's logical CPUs the process may use, and the LAW each side computes -- the CPU leg is the 2-D 12-flop reference law

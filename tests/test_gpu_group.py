@@ -252,7 +252,8 @@ def test_bench_under_torch_distributed_run_two_ranks(rx):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "32768", "--steps", "3", "--warmup", "1"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "32768", "--steps", "3", "--warmup", "1",
+           "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -261,15 +262,15 @@ def test_bench_under_torch_distributed_run_two_ranks(rx):
     assert res["n_gpus"] == 2 and res["config"]["host"] == "torch" and res["scaling"] == "strong"
     assert [r["slab"] for r in res["per_gpu"]] == [[0, 16384], [16384, 32768]] and all(r["force_launches"] == 3 for r in res["per_gpu"])
     assert res["value"] > 0 and 0 < res["roofline"]["frac"] < 1 and "cpu_baseline" not in res
-    assert res["verify"]["ok"] and res["verify"]["steps"] == 2, res["verify"]     # on by default with more than one GPU
+    assert res["verify"]["ok"] and res["verify"]["steps"] == 2, res["verify"]     # --full: on by default with more than one GPU
 
 
 def test_bench_default_line_has_roofline_and_measured_traffic(rx):
-    """N = 1 (the driver's line, at a small size): roofline + traffic measured by the in-run rocprofv3 passes when the
+    """N = 1 (the driver's `--full` line, at a small size): roofline + traffic measured by the in-run rocprofv3 passes when the
     profiler is installed."""
     import shutil
 
-    res = _run_bench(["--n", "32768", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5"], {})
+    res = _run_bench(["--full", "--n", "32768", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5"], {})
     assert res["n_gpus"] == 1 and res["config"]["host"] == "single"
     rl = res["roofline"]
     assert rl["hbm_algorithmic_bytes_per_launch"] == 16.0 * 32768 * 2
@@ -284,7 +285,7 @@ def test_bench_default_line_has_roofline_and_measured_traffic(rx):
 
 
 def test_bench_barnes_hut_workload(rx):
-    res = _run_bench(["--workload", "bh", "--n", "100000", "--steps", "3", "--warmup", "1"], {})
+    res = _run_bench(["--full", "--workload", "bh", "--n", "100000", "--steps", "3", "--warmup", "1"], {})
     assert res["unit"] == "body-steps/s" and res["value"] > 0
     assert res["ms_split"]["tree_nodes"] > 100000 and res["ms_split"]["bh_eval_kernel"] > 0
     assert res["cpu_baseline"]["rc"] == 0
@@ -307,6 +308,36 @@ def test_bench_barnes_hut_workload(rx):
     assert rl["unit"] == "TFLOP/s" and abs(rl["achieved"] - flops / (rl["kernel_avg_ms"] * 1e-3) / 1e12) <= 1e-9 * rl["achieved"]
     assert abs(rl["frac"] - rl["achieved"] / rl["peak"]) < 1e-12 and 0.0 < rl["frac"] < 0.5
     assert res["config"]["walk"].startswith("child groups")
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_state_of_its_last_timed_step(rx, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` does what its headline figure needs and nothing that takes a run of its
+    own (those sit behind --full); `--dump-outputs DIR` writes the state the last timed step left, one float32 .npy per array.
+    The kernels of the fast all-pairs step use no atomics, so a plain engine stepped W + K times from the same seeded state
+    must give the same bits."""
+    n, k, w = 4099, 3, 2                                                     # odd size: not a multiple of any tile
+    res = _run_bench(["--gpus", "1", "--n", str(n), "--steps", str(k), "--warmup", str(w), "--dump-outputs", str(tmp_path / "out")], {})
+    for key in ("cpu_baseline", "steady_state", "general_masses", "companions", "verify"):
+        assert key not in res, key
+    assert res["roofline"]["traffic"] is None and res["roofline"]["kernel_launches"] == k
+    assert res["steps"] == k and res["warmup"] == w and res["unit"] == "interactions/s" and res["higher_is_better"] is True
+    assert res["ms_per_step"] > 0 and abs(res["value"] - n * (n - 1.0) / (res["ms_per_step"] * 1e-3)) <= 1e-9 * res["value"]
+    g = rx.NBodyEngine()
+    g.plummer_sphere(n, dim=3)
+    st = g.get_particles()
+    g.close()
+    e = rx.NBodyEngine(mode="fast")
+    e.set_particles(st["px"], st["py"], st["vx"], st["vy"], st["m"], st["pz"], st["vz"])
+    for _ in range(w + k):
+        e.step_brute_force(0.01)
+    want = e.get_particles()
+    e.close()
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(key + ".npy" for key in want)
+    for key in want:
+        got = np.load(tmp_path / "out" / (key + ".npy"))
+        assert got.dtype == np.float32 and got.shape == (n,)
+        assert_bit_equal(got, want[key], key)
+    assert np.abs(want["vx"]).max() > 0
 
 
 LEVEL1 = r"""

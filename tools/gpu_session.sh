@@ -31,26 +31,26 @@ for stage in "$@"; do
     smoke) timeout 600 python __graft_entry__.py smoke > $O/${TAG}_smoke.log 2>&1; echo "smoke rc=$?" | tee -a $O/${TAG}_smoke.log ;;
     tests) timeout ${TEST_TIMEOUT:-3000} python -m pytest ${TESTS:-tests} -m gpu -q -x > $O/${TAG}_pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $O/${TAG}_pytest_gpu.log; tail -5 $O/${TAG}_pytest_gpu.log ;;
     bench)
-      timeout 900 python bench.py > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err; echo "bench rc=$?"; cat $O/${TAG}_bench_n1.json
+      timeout 900 python bench.py --full > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err; echo "bench rc=$?"; cat $O/${TAG}_bench_n1.json
       if [ "$(python -c 'import rust_exp_amd as r; print(r.device_count())' 2>/dev/null)" -ge 2 ]; then
-        timeout 900 python bench.py --gpus 2 > $O/${TAG}_bench_group2.json 2> $O/${TAG}_bench_group2.err
+        timeout 900 python bench.py --full --gpus 2 > $O/${TAG}_bench_group2.json 2> $O/${TAG}_bench_group2.err
       else
-        NBX_GROUP_EXCHANGE=copy timeout 900 python bench.py --gpus 2 --no-cpu-baseline > $O/${TAG}_bench_group2_one_gpu_copy.json 2> $O/${TAG}_bench_group2.err
+        NBX_GROUP_EXCHANGE=copy timeout 900 python bench.py --full --gpus 2 --no-cpu-baseline > $O/${TAG}_bench_group2_one_gpu_copy.json 2> $O/${TAG}_bench_group2.err
       fi
       echo "group bench rc=$?" ;;
     bh)
-      timeout 900 python bench.py --workload bh > $O/${TAG}_bench_bh_default.json 2> $O/${TAG}_bench_bh_default.err; echo "bh rc=$?"; cat $O/${TAG}_bench_bh_default.json
-      timeout 900 python bench.py --workload bh --bh-tree host --no-cpu-baseline > $O/${TAG}_bench_bh_host.json 2> $O/${TAG}_bench_bh_host.err
-      timeout 900 python bench.py --workload bh --bh-tree device --no-cpu-baseline > $O/${TAG}_bench_bh_device.json 2> $O/${TAG}_bench_bh_device.err
-      timeout 900 python bench.py --workload bh --bodies 10000 --theta 0.85 --no-cpu-baseline > $O/${TAG}_bench_bh_10000.json 2> $O/${TAG}_bench_bh_10000.err ;;
+      timeout 900 python bench.py --full --workload bh > $O/${TAG}_bench_bh_default.json 2> $O/${TAG}_bench_bh_default.err; echo "bh rc=$?"; cat $O/${TAG}_bench_bh_default.json
+      timeout 900 python bench.py --full --workload bh --bh-tree host --no-cpu-baseline > $O/${TAG}_bench_bh_host.json 2> $O/${TAG}_bench_bh_host.err
+      timeout 900 python bench.py --full --workload bh --bh-tree device --no-cpu-baseline > $O/${TAG}_bench_bh_device.json 2> $O/${TAG}_bench_bh_device.err
+      timeout 900 python bench.py --full --workload bh --bodies 10000 --theta 0.85 --no-cpu-baseline > $O/${TAG}_bench_bh_10000.json 2> $O/${TAG}_bench_bh_10000.err ;;
     prof)
-      (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OLDPWD/$O/${TAG}_prof -o p --output-format csv -- python $OLDPWD/bench.py --no-cpu-baseline --no-traffic > $OLDPWD/$O/${TAG}_prof_bench.json 2> $OLDPWD/$O/${TAG}_prof.err)
+      (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OLDPWD/$O/${TAG}_prof -o p --output-format csv -- python $OLDPWD/bench.py --full --no-cpu-baseline --no-traffic > $OLDPWD/$O/${TAG}_prof_bench.json 2> $OLDPWD/$O/${TAG}_prof.err)
       find $O/${TAG}_prof -name '*kernel_stats.csv' -exec cp {} $O/${TAG}_bench_kernel_stats.csv \; ; head -5 $O/${TAG}_bench_kernel_stats.csv ;;
     pmc)
       i=0
       for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_INST_CYCLES_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" "GRBM_GUI_ACTIVE GRBM_COUNT" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum"; do
         name=$(echo fetch write sq1 sq2 grbm tcc | cut -d' ' -f$((i+1))); i=$((i+1))
-        (cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc $grp -d $OLDPWD/$O/pmc_$name -o p --output-format csv -- python $OLDPWD/bench.py --no-cpu-baseline --no-traffic --steps 5 --warmup 1 > /dev/null 2> $OLDPWD/$O/pmc_$name.err)
+        (cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc $grp -d $OLDPWD/$O/pmc_$name -o p --output-format csv -- python $OLDPWD/bench.py --full --no-cpu-baseline --no-traffic --steps 5 --warmup 1 > /dev/null 2> $OLDPWD/$O/pmc_$name.err)
         f=$(find $O/pmc_$name -name '*counter_collection.csv' | head -1); [ -n "$f" ] && cp "$f" $O/pmc_$name/p_counter_collection.csv
       done ;;
     k1pmc)  # round 6: K1's counters in the round they are quoted -- both sweeps of the default bench line
@@ -59,7 +59,7 @@ for stage in "$@"; do
       for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "GRBM_GUI_ACTIVE GRBM_COUNT"; do
         name=$(echo fetch write sq1 grbm | cut -d' ' -f$((i+1))); i=$((i+1))
         rm -rf $O/pmc_$name
-        (cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc $grp -d $OLDPWD/$O/pmc_$name -o p --output-format csv -- python $OLDPWD/bench.py --no-cpu-baseline --no-traffic --no-companions --steady-seconds 0 --steps 5 --warmup 1 > /dev/null 2> $OLDPWD/$O/pmc_$name.err)
+        (cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc $grp -d $OLDPWD/$O/pmc_$name -o p --output-format csv -- python $OLDPWD/bench.py --full --no-cpu-baseline --no-traffic --no-companions --steady-seconds 0 --steps 5 --warmup 1 > /dev/null 2> $OLDPWD/$O/pmc_$name.err)
         f=$(find $O/pmc_$name -name '*counter_collection.csv' | head -1); [ -n "$f" ] && { cp -f "$f" $O/pmc_$name/p_counter_collection.csv 2>/dev/null; cp -f "$f" $O/${TAG}_pmc_${name}_counter_collection.csv; }
       done
       rm -rf $O/pmc_sq2 $O/pmc_tcc
@@ -72,13 +72,13 @@ for stage in "$@"; do
     shapes)
       timeout 1200 python tools/sweep_shapes.py > $O/${TAG}_shapes.log 2>&1
       for v in 6 ; do for s in 0 32 64 128; do   # (round 1 swept variant 5 here; removed in round 5)
-        timeout 300 python bench.py --shard-of 8 --variant $v --jsplit $s --no-cpu-baseline --no-traffic >> $O/${TAG}_shard_of_8.jsonl 2>> $O/${TAG}_shard.err
+        timeout 300 python bench.py --full --shard-of 8 --variant $v --jsplit $s --no-cpu-baseline --no-traffic >> $O/${TAG}_shard_of_8.jsonl 2>> $O/${TAG}_shard.err
       done; done ;;
     k1ab)   # K1 variants A/B: bench line + board power per variant, at the headline size, config #2's size and the 8-way shard shape
       for v in 1 6 7; do   # (variant 5 of the round-2 A/B was removed in round 5)
-        timeout 300 python bench.py --variant $v --no-cpu-baseline --no-traffic >> $O/${TAG}_k1ab_n262144.jsonl 2>> $O/${TAG}_k1ab.err
-        timeout 300 python bench.py --variant $v --n 65536 --no-cpu-baseline --no-traffic >> $O/${TAG}_k1ab_n65536.jsonl 2>> $O/${TAG}_k1ab.err
-        timeout 300 python bench.py --variant $v --shard-of 8 --no-cpu-baseline --no-traffic >> $O/${TAG}_k1ab_shard_of_8.jsonl 2>> $O/${TAG}_k1ab.err
+        timeout 300 python bench.py --full --variant $v --no-cpu-baseline --no-traffic >> $O/${TAG}_k1ab_n262144.jsonl 2>> $O/${TAG}_k1ab.err
+        timeout 300 python bench.py --full --variant $v --n 65536 --no-cpu-baseline --no-traffic >> $O/${TAG}_k1ab_n65536.jsonl 2>> $O/${TAG}_k1ab.err
+        timeout 300 python bench.py --full --variant $v --shard-of 8 --no-cpu-baseline --no-traffic >> $O/${TAG}_k1ab_shard_of_8.jsonl 2>> $O/${TAG}_k1ab.err
         timeout 300 python tools/power_probe.py 6 --variant $v > $O/${TAG}_power_k1_variant$v.json 2>> $O/${TAG}_k1ab.err
       done
       python - <<'PY'
@@ -92,9 +92,9 @@ PY
       ;;
     k1sweep)   # source-split sweep of the wave-split kernels at the three shapes that matter
       for v in 6 7; do
-        for sp in 2 4 8 16 32; do timeout 300 python bench.py --variant $v --jsplit $sp --no-cpu-baseline --no-traffic >> $O/${TAG}_k1sweep_n262144.jsonl 2>> $O/${TAG}_k1sweep.err; done
-        for sp in 2 4 8 16 32 64; do timeout 300 python bench.py --variant $v --jsplit $sp --n 65536 --no-cpu-baseline --no-traffic >> $O/${TAG}_k1sweep_n65536.jsonl 2>> $O/${TAG}_k1sweep.err; done
-        for sp in 8 16 32 64 128; do timeout 300 python bench.py --variant $v --jsplit $sp --shard-of 8 --no-cpu-baseline --no-traffic >> $O/${TAG}_k1sweep_shard_of_8.jsonl 2>> $O/${TAG}_k1sweep.err; done
+        for sp in 2 4 8 16 32; do timeout 300 python bench.py --full --variant $v --jsplit $sp --no-cpu-baseline --no-traffic >> $O/${TAG}_k1sweep_n262144.jsonl 2>> $O/${TAG}_k1sweep.err; done
+        for sp in 2 4 8 16 32 64; do timeout 300 python bench.py --full --variant $v --jsplit $sp --n 65536 --no-cpu-baseline --no-traffic >> $O/${TAG}_k1sweep_n65536.jsonl 2>> $O/${TAG}_k1sweep.err; done
+        for sp in 8 16 32 64 128; do timeout 300 python bench.py --full --variant $v --jsplit $sp --shard-of 8 --no-cpu-baseline --no-traffic >> $O/${TAG}_k1sweep_shard_of_8.jsonl 2>> $O/${TAG}_k1sweep.err; done
       done
       python - <<'PY' | tee gpurun_out/${TAG}_k1_wave_split_sweep.txt
 import json,glob
@@ -104,13 +104,13 @@ for f in sorted(glob.glob("gpurun_out/*_k1sweep_*.jsonl")):
 PY
       ;;
     cfgs)   # the other BASELINE configs on one GPU + the 2-D kernel on the headline size
-      timeout 600 python bench.py --bodies 65536 --steps 20 --warmup 3 --no-traffic > $O/${TAG}_bench_cfg2_20_steps.json 2>> $O/${TAG}_cfgs.err
-      timeout 600 python bench.py --bodies 65536 --steps 400 --warmup 100 --no-traffic > $O/${TAG}_bench_cfg2.json 2>> $O/${TAG}_cfgs.err
-      timeout 600 python bench.py --workload two_galaxies --bodies 524288 --source-bits 16 --cpu-seconds 4 --no-general-masses > $O/${TAG}_bench_cfg5_1gpu.json 2>> $O/${TAG}_cfgs.err
-      timeout 600 python bench.py --workload two_galaxies --bodies 524288 --no-traffic --no-cpu-baseline > $O/${TAG}_bench_cfg5_1gpu_fp32.json 2>> $O/${TAG}_cfgs.err
-      timeout 600 python bench.py --dim 2 --no-traffic --no-cpu-baseline > $O/${TAG}_bench_n1_dim2.json 2>> $O/${TAG}_cfgs.err
-      timeout 600 python bench.py --workload stable_orbits --no-traffic --no-cpu-baseline > $O/${TAG}_bench_stable_orbits_262144.json 2>> $O/${TAG}_cfgs.err
-      for m in strict; do for nb in 10000 65536 262144; do timeout 600 python bench.py --mode $m --bodies $nb --no-traffic --no-cpu-baseline >> $O/${TAG}_bench_strict.jsonl 2>> $O/${TAG}_cfgs.err; done; done
+      timeout 600 python bench.py --full --bodies 65536 --steps 20 --warmup 3 --no-traffic > $O/${TAG}_bench_cfg2_20_steps.json 2>> $O/${TAG}_cfgs.err
+      timeout 600 python bench.py --full --bodies 65536 --steps 400 --warmup 100 --no-traffic > $O/${TAG}_bench_cfg2.json 2>> $O/${TAG}_cfgs.err
+      timeout 600 python bench.py --full --workload two_galaxies --bodies 524288 --source-bits 16 --cpu-seconds 4 --no-general-masses > $O/${TAG}_bench_cfg5_1gpu.json 2>> $O/${TAG}_cfgs.err
+      timeout 600 python bench.py --full --workload two_galaxies --bodies 524288 --no-traffic --no-cpu-baseline > $O/${TAG}_bench_cfg5_1gpu_fp32.json 2>> $O/${TAG}_cfgs.err
+      timeout 600 python bench.py --full --dim 2 --no-traffic --no-cpu-baseline > $O/${TAG}_bench_n1_dim2.json 2>> $O/${TAG}_cfgs.err
+      timeout 600 python bench.py --full --workload stable_orbits --no-traffic --no-cpu-baseline > $O/${TAG}_bench_stable_orbits_262144.json 2>> $O/${TAG}_cfgs.err
+      for m in strict; do for nb in 10000 65536 262144; do timeout 600 python bench.py --full --mode $m --bodies $nb --no-traffic --no-cpu-baseline >> $O/${TAG}_bench_strict.jsonl 2>> $O/${TAG}_cfgs.err; done; done
       python - <<'PY'
 import json,glob
 for f in sorted(glob.glob("gpurun_out/*_bench_cfg*.json")+glob.glob("gpurun_out/*_bench_n1_dim2.json")+glob.glob("gpurun_out/*_bench_stable_orbits_*.json")):
@@ -134,8 +134,8 @@ PY
       timeout 1500 python tools/scale_model.py > $O/${TAG}_scaling_bound.json 2> $O/${TAG}_scaling_bound.err; echo "scale rc=$?"; cut -c1-600 $O/${TAG}_scaling_bound.json ;;
     verify8)   # the self-validating multi-GPU line on whatever this box has (8 engines share one GPU through peer copies otherwise)
       if [ "$(python -c 'import rust_exp_amd as r; print(r.device_count())' 2>/dev/null)" -ge 8 ]; then X=""; else X="NBX_GROUP_EXCHANGE=copy"; fi
-      env $X timeout 900 python bench.py --gpus 8 --verify --no-cpu-baseline > $O/${TAG}_bench_group8_verify.json 2> $O/${TAG}_bench_group8_verify.err; echo "verify8 rc=$?"; cut -c1-800 $O/${TAG}_bench_group8_verify.json
-      env $X NBX_GROUP_ENQUEUE=threads timeout 900 python bench.py --gpus 8 --verify --no-cpu-baseline > $O/${TAG}_bench_group8_verify_threads.json 2>> $O/${TAG}_bench_group8_verify.err; echo "verify8 threads rc=$?" ;;
+      env $X timeout 900 python bench.py --full --gpus 8 --verify --no-cpu-baseline > $O/${TAG}_bench_group8_verify.json 2> $O/${TAG}_bench_group8_verify.err; echo "verify8 rc=$?"; cut -c1-800 $O/${TAG}_bench_group8_verify.json
+      env $X NBX_GROUP_ENQUEUE=threads timeout 900 python bench.py --full --gpus 8 --verify --no-cpu-baseline > $O/${TAG}_bench_group8_verify_threads.json 2>> $O/${TAG}_bench_group8_verify.err; echo "verify8 threads rc=$?" ;;
     fold)   # device quadtree with the reference fold vs exact sums vs host tree: bit-equality + ms per step by size; kernel trace
       timeout 900 python tools/bh_fold_probe.py 0.85 > $O/${TAG}_bh_fold_probe.jsonl 2> $O/${TAG}_bh_fold_probe.err; cut -c1-60,130-420 $O/${TAG}_bh_fold_probe.jsonl
       bash tools/prof_bh_fold.sh > /dev/null 2>&1

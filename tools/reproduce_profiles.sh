@@ -4,6 +4,7 @@
 # and copy the gpurun_out/<TAG>_* files named in profiles/README.md into profiles/.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 T=${TAG:-r02}
+O=${OUT:-bench_out}; mkdir -p $O   # where the bench.py --full lines below write (OUT=<the folder of the other lines> to keep them together)
 bash tools/gpu_session.sh smoke tests bench bh prof pmc power k1ab k1sweep cfgs shapes ubench strict fuzz
 # round 3: the self-validating 8-engine line, the exchange floor + scaling bound, the reference-fold device tree (probe, kernel
 # stats), the level-1 frame loops, the hand-over rates of long runs; then the soak and the crossover tables
@@ -25,14 +26,14 @@ python tools/bh_walk_trace.py > gpurun_out/${T}_bh_walk_trace_1m.json 2> gpurun_
 [ -x tools/ubench_sort_cfg ] || hipcc --offload-arch=gfx950 -O3 tools/ubench_sort_cfg.hip -o tools/ubench_sort_cfg
 tools/ubench_sort_cfg > gpurun_out/${T}_ubench_sort_cfg.txt 2>&1
 NBX_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --dry-run --bodies 65536 > gpurun_out/${T}_bench_torch2_gloo_one_gpu_dry_run.json 2> /dev/null
-NBX_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 5 --warmup 1 --bodies 65536 --no-cpu-baseline > gpurun_out/${T}_bench_torch2_gloo_one_gpu.json 2> /dev/null
+NBX_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 2 --steps 5 --warmup 1 --bodies 65536 --no-cpu-baseline > $O/${T}_bench_torch2_gloo_one_gpu.json 2> /dev/null
 python tools/bh_union_model.py 1048576 > gpurun_out/${T}_bh_walk_union_model_n1048576.json 2> /dev/null   # (CPU: needs no GPU)
 # round 5: the driver's line with its companions (configs #2, #4, #5), the Barnes-Hut line on the host tree (traffic of the wave walk
 # alone), kernel stats of the 1 M-body step, the bucket-sort shapes, long runs of the warm sort (fallback rates), the frame loops.
 # (The walk-split A/B -- profiles/r05_bh_walk_split_ab.jsonl, r05_bh_walk_trace_1m_split*.json -- was measured on a tree that still
 #  had the experiment: commit cc66460, `NBX_WALK_SPLIT_PCT=25 python tools/bh_walk_trace.py`, `bash tools/bh_walk_split_ab.sh`.)
-python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${T}_bench_n1_companions.json 2> gpurun_out/${T}_bench.err
-python bench.py --workload bh --bh-tree host --steps 10 --warmup 2 --steady-seconds 0 --no-accuracy > gpurun_out/${T}_bench_bh_host.json 2> /dev/null
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench_n1_companions.json 2> $O/${T}_bench.err
+python bench.py --full --workload bh --bh-tree host --steps 10 --warmup 2 --steady-seconds 0 --no-accuracy > $O/${T}_bench_bh_host.json 2> /dev/null
 (cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --stats -d /tmp/nbx_bh_stats5 -o p --output-format csv -- python $OLDPWD/bench.py --workload bh --no-cpu-baseline --no-traffic --steps 40 --warmup 5 --steady-seconds 0 > /dev/null 2>&1); find /tmp/nbx_bh_stats5 -name '*kernel_stats.csv' -exec cp {} gpurun_out/${T}_bh_kernel_stats_1m.csv \;
 [ -x tools/ubench_bucket_sort ] || hipcc --offload-arch=gfx950 -O3 tools/ubench_bucket_sort.hip -o tools/ubench_bucket_sort
 (for a in "1048576 800 0" "1048576 640 4" "1048576 640 4 10" "262144 640 4"; do tools/ubench_bucket_sort $a; done) > gpurun_out/${T}_ubench_bucket_sort.txt 2>&1
@@ -52,6 +53,6 @@ NBX_LONG_STEPS=1000 python tools/bh_warm_long_run.py random_disk:65536 stable_or
 python tools/bh_dense_probe.py --accuracy 1048576 2097152 4194304 > gpurun_out/${T}_bh_dense_probe.jsonl 2> /dev/null
 python tools/bh_reference_fold_async_probe.py > gpurun_out/${T}_bh_reference_fold_async_probe.txt 2>&1
 bash tools/gpu_session.sh k1pmc
-for r in 1 2 3; do for pipe in 0 1; do echo -n "pipe $pipe "; NBX_BH_WALK_PIPE=$pipe python bench.py --workload bh --no-cpu-baseline --no-traffic --steps 40 --warmup 5 --steady-seconds 0 2> /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms/step %.4f traversal_ms %.4f' % (d['ms_per_step'], d['roofline']['kernel_avg_ms']))"; done; done > gpurun_out/${T}_bh_walk_pipelined_ab.txt
+for r in 1 2 3; do for pipe in 0 1; do echo -n "pipe $pipe "; NBX_BH_WALK_PIPE=$pipe python bench.py --full --workload bh --no-cpu-baseline --no-traffic --steps 40 --warmup 5 --steady-seconds 0 2> /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms/step %.4f traversal_ms %.4f' % (d['ms_per_step'], d['roofline']['kernel_avg_ms']))"; done; done > $O/${T}_bh_walk_pipelined_ab.txt
 python tests/fuzz_fast.py 60000 3000 > gpurun_out/${T}_fuzz_fast.txt 2>&1; python tests/fuzz_strict.py 60000 300 > gpurun_out/${T}_fuzz_strict.txt 2>&1
 python tests/fuzz_api.py 60000 100 > gpurun_out/${T}_fuzz_api.txt 2>&1; python tests/fuzz_group.py 60000 500 > gpurun_out/${T}_fuzz_group.txt 2>&1
