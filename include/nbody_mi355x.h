@@ -93,7 +93,7 @@ enum nbx_status {
     NBX_ERR_STATE = -7       /* call not valid in the engine's current configuration */
 };
 
-/* 14 options (numbers are stable; 10-12 and 17 moved to nbx_stat, 16 and 19 -- measured losers -- were removed in round 5) */
+/* 15 options (numbers are stable; 10-12 and 17 moved to nbx_stat, 16 and 19 -- measured losers -- were removed in round 5) */
 enum nbx_option {
     /* 0 = fast (default): a_i = sum_j m_j d/(|d|^2+eps) with v_rcp_f32 + FMA, tile order,
      *     parity within the stated fp32 tolerance.
@@ -165,6 +165,18 @@ enum nbx_option {
                                     * reads no other body's position from the particle array -- the group records hold copies);
                                     * 0 = separate kick-drift kernel (the A/B: 0.0932 -> 0.0899 ms per step at 10 000 bodies,
                                     * 0.8375 -> 0.8252 at 1 048 576) */
+    NBX_OPT_BH_DIM = 22,           /* (21 is not an option.)  Barnes-Hut tree: 2 (default) = the quadtree on (x, y) of every mode above, z
+                                    * ignored, as the planar reference; 3 = the OCTREE path: nbx_step_barnes_hut(theta != 0) and
+                                    * nbx_forces(theta != 0) build an octree on the device every step (the reference's rules with z
+                                    * added: per-axis root AABB, midpoint children, child index 4 (z < cz) + 2 (y < cy) + (x >= cx), 21
+                                    * levels, bodies of one level-21 cell = one leaf, interior records = roundings of exact fp64 sums)
+                                    * and walk it once per wave with the reference's opening test on (dx*dx + dy*dy) + dz*dz;
+                                    * nbx_forces fills fz; the kill box (nbody.rs:466-471) zeroes all three velocity components
+                                    * outside +-55 on ANY axis (z origin 0).  Tolerance class: the exact-sum class's.
+                                    * Fast mode on one unsharded engine with fp32 sources: the bit-exact mode, world > 1, an engine of
+                                    * an nbx_group and NBX_OPT_SOURCE_PRECISION = 16 return NBX_ERR_STATE.  A root box so large that
+                                    * two bodies further apart than EPS share a level-21 cell: NBX_ERR_TREE_DEPTH, state untouched.
+                                    * There is no "auto": the default never changes behaviour */
     NBX_OPT_SOURCE_PRECISION = 6   /* 32 (default) or 16: all-pairs SOURCES read from a half4 (x,y,z,m) copy, 8 B/body;
                                     * targets, accumulators and the integrated state stay fp32 (fast mode only) */
 };
@@ -306,6 +318,11 @@ int32_t nbx_bh_tree_dump(nbx_engine *e, float *rows, int32_t cap);
  * {float px, py, m, s; int32 skip, interior, pad, pad}. threaded = 1 uses the host-thread flattener
  * (same bytes), 2 dumps the DEVICE-built tree (needs a GPU). Returns the node count; writes only when cap >= count. Runs without a device. */
 int32_t nbx_bh_flat_dump(nbx_engine *e, void *rows, int32_t cap, int32_t threaded);
+
+/* The 3-D sibling: the OCTREE of the current state (NBX_OPT_BH_DIM = 3 walks it), built on the device (needs a GPU) whatever the
+ * option says.  Pre-order, empty children dropped, 32-byte records {float px, py, pz, m; float s; int32 skip, interior, pad} with
+ * s = the x-extent of the node's box.  Returns the node count; writes only when cap >= count. */
+int32_t nbx_bh_oct_dump(nbx_engine *e, void *rows, int32_t cap);
 
 /* ---- multi-GPU: bodies shard as contiguous slabs of targets, the reference's own thread split  */
 /* (range = N/world, last rank takes the remainder; nbody.rs:426-428).  One process per GPU; every */

@@ -65,7 +65,7 @@ int32_t nbx_set_option(nbx_engine* e, int32_t option, int64_t value)
     switch (option) {   // a step that is still in flight was issued under the CURRENT options: settle it (and redo it, if its device
                         // build was refused) before any option that shapes a step changes
         case NBX_OPT_FORCE_MODE: case NBX_OPT_BH_TREE: case NBX_OPT_BH_FOLD: case NBX_OPT_BH_WAVE: case NBX_OPT_BH_ASYNC:
-        case NBX_OPT_SOURCE_PRECISION: case NBX_OPT_BH_WALK: case NBX_OPT_BH_FUSE_KICK: {
+        case NBX_OPT_SOURCE_PRECISION: case NBX_OPT_BH_WALK: case NBX_OPT_BH_FUSE_KICK: case NBX_OPT_BH_DIM: {
             const int rc = resolve_pending(e);
             if (rc != NBX_OK) return rc;
             break;
@@ -133,6 +133,10 @@ int32_t nbx_set_option(nbx_engine* e, int32_t option, int64_t value)
             if (value != 0 && value != 1) return fail(NBX_ERR_INVALID, "bh fuse kick must be 0 or 1");
             e->bh_fuse_kick = (int)value;
             return NBX_OK;
+        case NBX_OPT_BH_DIM:
+            if (value != 2 && value != 3) return fail(NBX_ERR_INVALID, "bh dim must be 2 (quadtree on x, y) or 3 (octree)");
+            e->bh_dim = (int)value;
+            return NBX_OK;
         case NBX_OPT_BH_FOLD:
             if (value != 0 && value != 1 && value != -1) return fail(NBX_ERR_INVALID, "bh fold must be 0 (exact sums), 1 (reference fold) or -1 (by size)");
             e->bh_fold = (int)value;
@@ -170,6 +174,7 @@ int64_t nbx_get_option(const nbx_engine* e, int32_t option)
         case NBX_OPT_BH_ASYNC: return e->bh_async;
         case NBX_OPT_BH_WALK: return e->bh_walk;
         case NBX_OPT_BH_FUSE_KICK: return e->bh_fuse_kick;
+        case NBX_OPT_BH_DIM: return e->bh_dim;
         default: return NBX_ERR_INVALID;
     }
 }
@@ -207,6 +212,7 @@ int32_t nbx_query_option(const nbx_engine* e, int32_t option, int64_t* value)
         case NBX_OPT_FORCE_MODE: case NBX_OPT_JSPLIT: case NBX_OPT_BODIES_PER_THREAD: case NBX_OPT_DIM: case NBX_OPT_PROFILE:
         case NBX_OPT_KERNEL_VARIANT: case NBX_OPT_SOURCE_PRECISION: case NBX_OPT_DRAW_DEVICE: case NBX_OPT_BH_TREE: case NBX_OPT_BH_WAVE:
         case NBX_OPT_STRICT_KERNEL: case NBX_OPT_BH_FOLD: case NBX_OPT_BH_ASYNC: case NBX_OPT_BH_WALK: case NBX_OPT_BH_FUSE_KICK:
+        case NBX_OPT_BH_DIM:
             if (value) *value = nbx_get_option(e, option);
             return NBX_OK;
         default:
@@ -368,11 +374,15 @@ int32_t nbx_synchronize(nbx_engine* e)
 int32_t nbx_forces(nbx_engine* e, float theta, int32_t cap, float* fx, float* fy, float* fz)
 {
     if (!e) return fail(NBX_ERR_INVALID, "null engine");
-    int rc = upload(e);
+    const bool octree = theta != 0.0f && e->bh_dim == 3;   // (theta == 0: all-pairs, which honours z already)
+    int rc = octree ? bh3_refusal(e) : NBX_OK;
+    if (rc != NBX_OK) return rc;
+    rc = upload(e);
     if (rc != NBX_OK) return rc;
     const int slab = e->slab();
     if (cap < slab) return fail(NBX_ERR_INVALID, "capacity %d < slab %d", cap, slab);
     if (slab == 0) return 0;
+    if (octree) return forces_bh3(e, theta, fx, fy, fz);
     if (theta == 0.0f && e->force_mode == 0) {
         rc = launch_forces_fast(e);
         if (rc != NBX_OK) return rc;
@@ -555,6 +565,12 @@ int32_t nbx_bh_flat_dump(nbx_engine* e, void* rows, int32_t cap, int32_t threade
     if ((size_t)cap >= e->flat_small.size() && rows && !e->flat_small.empty())
         std::memcpy(rows, e->flat_small.data(), sizeof(nbx::BhNode) * e->flat_small.size());
     return (int32_t)e->flat_small.size();
+}
+
+int32_t nbx_bh_oct_dump(nbx_engine* e, void* rows, int32_t cap)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return oct_dump(e, rows, cap);
 }
 
 // ---- checkpoint: the reference has none (state is lost on every experiment switch) ----

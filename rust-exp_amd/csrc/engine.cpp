@@ -387,6 +387,10 @@ void free_device(nbx_engine* e)
     if (e->d_sorted_pos) (void)hipFree(e->d_sorted_pos);
     if (e->d_nodes) (void)hipFree(e->d_nodes);
     if (e->d_groups) (void)hipFree(e->d_groups);
+    if (e->d_oct_ws) (void)hipFree(e->d_oct_ws);
+    if (e->d_oct_nodes) (void)hipFree(e->d_oct_nodes);
+    if (e->d_oct_groups) (void)hipFree(e->d_oct_groups);
+    if (e->h_oct_counters) (void)hipHostFree(e->h_oct_counters);
     if (e->d_guard) (void)hipFree(e->d_guard);
     if (e->d_exc_idx) (void)hipFree(e->d_exc_idx);
     if (e->d_src4) (void)hipFree(e->d_src4);

@@ -539,6 +539,7 @@ static int step_bh_async(nbx_engine* e, float theta, float dt)
 
 int step_bh(nbx_engine* e, float theta, float dt)
 {
+    if (e->bh_dim == 3) return step_bh3(e, theta, dt);   // NBX_OPT_BH_DIM: the octree path (engine_bh3.cpp)
     int rc = NBX_OK;
     if (e->any_pending() && (e->bh_refusal_streak[0] > 0 || e->bh_refusal_streak[1] > 0)) {   // a verdict that may start a back-off: read it before choosing the path
         rc = resolve_pending(e);
@@ -595,6 +596,7 @@ int step_bh(nbx_engine* e, float theta, float dt)
 int step_bh_group(nbx_engine* const* eng, int count, float theta, float dt)
 {
     if (count == 1) return step_bh(eng[0], theta, dt);
+    if (eng[0]->bh_dim == 3) return bh3_refusal(eng[0]);   // (NBX_ERR_STATE: the octree path serves no group)
     for (int d = 0; d < count; d++) {
         const int rc = upload(eng[d]);
         if (rc != NBX_OK) return rc;

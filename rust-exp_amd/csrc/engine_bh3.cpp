@@ -1,0 +1,143 @@
+// engine_bh3.cpp -- the 3-D Barnes-Hut path (NBX_OPT_BH_DIM = 3): octree built on the device (bh_oct.hip), walked once per wave
+// (bh_oct_walk.hip).  Step, forces-only evaluation and the dump of the tree.  The build is cold every step and the host reads the
+// node count between its two halves (one small synchronous read); the gated asynchronous pipeline, the warm sort, the bit-exact
+// mode, sharded and group engines and the fp16 source copy of the quadtree path are not served here: NBX_ERR_STATE.
+#include "engine_internal.h"
+
+namespace nbxi {
+
+static constexpr int kOctMaxBodies = 1 << 25;   // node slots are 32-bit and a body can start up to 22 nodes
+
+int bh3_refusal(const nbx_engine* e)
+{
+    if (e->force_mode != 0) return fail(NBX_ERR_STATE, "NBX_OPT_BH_DIM = 3: the octree path has no bit-exact (strict) mode");
+    if (e->world > 1) return fail(NBX_ERR_STATE, "NBX_OPT_BH_DIM = 3: the octree path does not serve a sharded engine (world = %d)", e->world);
+    if (e->in_group) return fail(NBX_ERR_STATE, "NBX_OPT_BH_DIM = 3: the octree path does not serve an engine inside an nbx_group");
+    if (e->source_half) return fail(NBX_ERR_STATE, "NBX_OPT_BH_DIM = 3: the octree path does not serve the fp16 source copy");
+    if (e->n > kOctMaxBodies) return fail(NBX_ERR_STATE, "NBX_OPT_BH_DIM = 3: more than %d bodies", kOctMaxBodies);
+    // (the reference asserts a positive mass where it folds one into a node, nbody.rs:304)
+    if (e->n > 0 && !(e->mass_min > 0.0f)) return fail(NBX_ERR_TREE, "octree build: a mass is not positive and finite (nbody.rs:304)");
+    return NBX_OK;
+}
+
+// the octree of the current device state into e->d_oct_nodes; *order = the bodies in key order (device pointer into the workspace)
+static int oct_build(nbx_engine* e, int* n_nodes, int* n_leaves, int* depth, const unsigned** order)
+{
+    HIP_TRY(hipSetDevice(e->device));
+    size_t sort_tmp = 0;
+    const size_t need = nbx::oct_workspace_bytes(e->n, &sort_tmp);
+    if (need > e->oct_ws_bytes) {
+        if (e->d_oct_ws) HIP_TRY(hipFree(e->d_oct_ws));
+        e->d_oct_ws = nullptr;
+        e->oct_ws_bytes = 0;
+        HIP_TRY(hipMalloc(&e->d_oct_ws, need + need / 8));
+        e->oct_ws_bytes = need + need / 8;
+    }
+    if (!e->h_oct_counters) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->h_oct_counters), 64, hipHostMallocDefault));
+    {
+        ProfScope ps(e, NBX_K_TREE_BUILD);
+        HIP_TRY(nbx::oct_build_scan(e->d_posm, e->n, e->d_oct_ws, sort_tmp, e->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(e->h_oct_counters, nbx::oct_counters(e->d_oct_ws), 4 * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(wait_stream(e->stream, e->n <= kSpinMaxBodies));
+    const int* c = e->h_oct_counters;
+    if (c[2] > 0)
+        return fail(NBX_ERR_TREE_DEPTH, "octree: %d leaves of level %d hold bodies further apart than EPS (the root box is too large for %d "
+                                        "levels; the reference panics on its depth here, nbody.rs:230-232)", c[2], nbx::kOctLevels, nbx::kOctLevels);
+    if (c[0] <= 0 || c[1] <= 0 || c[1] > c[0]) return fail(NBX_ERR_TREE, "octree build: %d nodes, %d leaves for %d bodies", c[0], c[1], e->n);
+    // node and group arrays follow the count: no build is refused for pool size
+    int rc = grow(&e->d_oct_nodes, &e->oct_nodes_cap, (size_t)c[0] + (size_t)c[0] / 8);
+    if (rc != NBX_OK) return rc;
+    {
+        ProfScope ps(e, NBX_K_TREE_BUILD);
+        HIP_TRY(nbx::oct_build_emit(e->n, e->d_oct_ws, sort_tmp, c[0], e->d_oct_nodes, e->stream));
+    }
+    *n_nodes = c[0];
+    *n_leaves = c[1];
+    *depth = c[3];
+    if (order) *order = nbx::oct_order(e->d_oct_ws, e->n, sort_tmp);
+    return NBX_OK;
+}
+
+// build + groups + walk; kick: the walk ends the step, else F = m a into e->d_out4
+static int oct_evaluate(nbx_engine* e, float theta, bool kick, float dt, int* n_nodes, int* depth)
+{
+    int leaves = 0;
+    const unsigned* order = nullptr;
+    int rc = oct_build(e, n_nodes, &leaves, depth, &order);
+    if (rc != NBX_OK) return rc;
+    const size_t records = (size_t)(*n_nodes - leaves) + 1;   // one per interior node + the root's own
+    rc = grow(&e->d_oct_groups, &e->oct_groups_cap, records + records / 8);
+    if (rc != NBX_OK) return rc;
+    if (!kick) {
+        rc = grow(&e->d_out4, &e->out4_cap, (size_t)e->n);
+        if (rc != NBX_OK) return rc;
+    }
+    ProfScope ps(e, NBX_K_BH_EVAL);
+    HIP_TRY(nbx::launch_oct_groups(e->d_oct_nodes, *n_nodes, theta, e->d_oct_groups, e->stream));
+    HIP_TRY(nbx::launch_oct_walk(e->d_posm, e->n, order, e->d_oct_groups, kick ? nullptr : e->d_out4, kick ? e->d_vel : nullptr, dt, e->stream));
+    return NBX_OK;
+}
+
+int step_bh3(nbx_engine* e, float theta, float dt)
+{
+    int rc = bh3_refusal(e);
+    if (rc != NBX_OK) return rc;
+    rc = resolve_pending(e);
+    if (rc != NBX_OK) return rc;
+    rc = upload(e);
+    if (rc != NBX_OK) return rc;
+    if (e->n == 0) return NBX_OK;
+    int nodes = 0, depth = 0;
+    rc = oct_evaluate(e, theta, /*kick=*/true, dt, &nodes, &depth);
+    if (rc != NBX_OK) return rc;   // (NBX_ERR_TREE_DEPTH: nothing behind the scans ran, the state is untouched)
+    e->positions_moved();
+    e->sort_warm_n = 0;            // the quadtree build's order is of a state this step has left behind
+    e->host_pos_valid = false;
+    e->host_vel_valid = false;
+    if (log_enabled())
+        std::fprintf(stderr, "[nbx] step_barnes_hut dev=%d n=%d theta=%g dt=%g mode=fast dim=3 tree=device nodes=%d depth=%d walk=wave\n",
+                     e->device, e->n, (double)theta, (double)dt, nodes, depth);
+    return NBX_OK;
+}
+
+int forces_bh3(nbx_engine* e, float theta, float* fx, float* fy, float* fz)
+{
+    int rc = bh3_refusal(e);
+    if (rc != NBX_OK) return rc;
+    rc = resolve_pending(e);
+    if (rc != NBX_OK) return rc;
+    rc = upload(e);
+    if (rc != NBX_OK) return rc;
+    if (e->n == 0) return 0;
+    int nodes = 0, depth = 0;
+    rc = oct_evaluate(e, theta, /*kick=*/false, 0.0f, &nodes, &depth);
+    if (rc != NBX_OK) return rc;
+    std::vector<float4> tmp((size_t)e->n);
+    HIP_TRY(hipMemcpyAsync(tmp.data(), e->d_out4, sizeof(float4) * (size_t)e->n, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < e->n; i++) {
+        if (fx) fx[i] = tmp[(size_t)i].x;
+        if (fy) fy[i] = tmp[(size_t)i].y;
+        if (fz) fz[i] = tmp[(size_t)i].z;
+    }
+    return e->n;
+}
+
+int oct_dump(nbx_engine* e, void* rows, int cap)
+{
+    if (e->n > kOctMaxBodies) return fail(NBX_ERR_STATE, "octree: more than %d bodies", kOctMaxBodies);
+    int rc = resolve_pending(e);
+    if (rc != NBX_OK) return rc;
+    rc = upload(e);
+    if (rc != NBX_OK) return rc;
+    if (e->n == 0) return 0;
+    int nodes = 0, leaves = 0, depth = 0;
+    rc = oct_build(e, &nodes, &leaves, &depth, nullptr);
+    if (rc != NBX_OK) return rc;
+    if (rows && cap >= nodes) HIP_TRY(hipMemcpyAsync(rows, e->d_oct_nodes, sizeof(nbx::OctNode) * (size_t)nodes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return nodes;
+}
+
+}  // namespace nbxi

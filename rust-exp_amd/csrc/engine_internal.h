@@ -114,6 +114,17 @@ struct nbx_engine {
         if (bh_fold >= 0) return bh_fold;
         return n <= (force_mode != 0 ? nbx::kFoldFaithfulMax : nbx::kFoldCostMax) ? 1 : 0;
     }
+    // NBX_OPT_BH_DIM: 2 (default) = the quadtree path on (x, y), z ignored; 3 = the octree path (engine_bh3.cpp: bh_oct.hip builds,
+    // bh_oct_walk.hip walks).  Fast mode, one unsharded engine outside a group, fp32 sources: anything else is NBX_ERR_STATE
+    int bh_dim = 2;
+    bool in_group = false;         // member of an nbx_group (set by nbx_group_create)
+    void* d_oct_ws = nullptr;      // octree build workspace
+    size_t oct_ws_bytes = 0;
+    nbx::OctNode* d_oct_nodes = nullptr;
+    size_t oct_nodes_cap = 0;
+    nbx::OctGroup* d_oct_groups = nullptr;
+    size_t oct_groups_cap = 0;
+    int* h_oct_counters = nullptr; // pinned: nodes, leaves, leaves wider than EPS, depth of the last octree build
     int bh_wave = 1;               // wave-uniform traversal when a spatial body order is available
     // A Barnes-Hut step on the device tree is enqueued WITHOUT waiting for the build's verdict (node count, EPS clusters): walk
     // and kick-drift are gated on the device by the build's own counters.  The host reads the verdict at the next call that
@@ -415,6 +426,11 @@ int step_bh_group(nbx_engine* const* eng, int count, float theta, float dt);
 int spatial_order(nbx_engine* e);
 int slab_order(nbx_engine* e);
 int step_bh(nbx_engine* e, float theta, float dt);
+// engine_bh3.cpp: the 3-D Barnes-Hut path (NBX_OPT_BH_DIM = 3)
+int bh3_refusal(const nbx_engine* e);   // NBX_OK, or the status of a configuration the octree path does not serve (text in nbx_last_error)
+int step_bh3(nbx_engine* e, float theta, float dt);
+int forces_bh3(nbx_engine* e, float theta, float* fx, float* fy, float* fz);
+int oct_dump(nbx_engine* e, void* rows, int cap);
 int resolve_pending(nbx_engine* e);   // the verdicts of the speculatively enqueued Barnes-Hut steps, oldest first (no-op when none)
 void free_device(nbx_engine* e);
 uint64_t entropy_seed();

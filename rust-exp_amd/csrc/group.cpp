@@ -474,6 +474,7 @@ int32_t nbx_group_create(nbx_group** out, const int32_t* devices, int32_t count)
         if (nbx_create(&e, dev) != NBX_OK) { nbx_group_destroy(g); return NBX_ERR_ALLOC; }
         e->rank = i;
         e->world = count;
+        e->in_group = true;
         g->eng.push_back(e);
         g->devices.push_back(dev);
     }

@@ -62,6 +62,41 @@ hipError_t launch_bh_count_groups(const float4* posm, int lo, int n_targets, con
                                                          // interior nodes), [3] groups loaded (per body)
 hipError_t launch_bh_thresholds(const float* s, const float* theta, float* out, int count, hipStream_t stream);   // test hook
 
+// ---- 3-D Barnes-Hut (NBX_OPT_BH_DIM = 3): the octree built on the device (bh_oct.hip) and walked once per wave (bh_oct_walk.hip) ----
+constexpr int kOctLevels = 21;   // 63-bit keys, 3 bits per level
+// pre-order record, empty children dropped (what nbx_bh_oct_dump returns): 32 bytes
+struct OctNode {
+    float px, py, pz, m;     // centre of mass (a single-body leaf: the body itself) and mass
+    float s;                 // x-extent of the node's box (the reference's opening test uses x alone, nbody.rs:341)
+    int32_t skip;            // slot behind the node's subtree
+    int32_t interior;        // 1 = has children
+    int32_t rank;            // interior nodes before this one in pre-order (where k_oct_groups files its children); 0 for a leaf
+};
+// One record per OPENED node, in depth-first order: record r + 1 = the children of the r-th interior node, record 0 = the root alone.
+// 8 x (x, y, z, m) = two 16-dword loads, then 8 thresholds T (bh_threshold.h; -1 = leaf: always evaluated, +inf = absent) and 8 child
+// words (>= 0: index of the child's own record, kOctLeaf, kOctAbsent).  Present children first, in child-index order.
+constexpr int kOctLeaf = -1, kOctAbsent = -2;
+struct alignas(64) OctGroup {
+    float4 c[8];
+    float T[8];
+    int32_t kid[8];
+};
+static_assert(sizeof(OctNode) == 32 && sizeof(OctGroup) == 192, "layouts shared with the kernels and the dump");
+// build counters the host reads between the two halves: [0] nodes, [1] leaves, [2] multi-body leaves whose bodies are not within EPS
+// of each other (a root box so large that a level-21 cell is wider than EPS: the analogue of the reference's depth panic), [3] depth
+size_t oct_workspace_bytes(int n, size_t* sort_tmp_bytes);
+const int* oct_counters(const void* workspace);
+const unsigned* oct_order(void* workspace, int n, size_t sort_tmp_bytes);   // body indices in key order (valid after oct_build_scan)
+// root box, keys, sort, scans: everything up to the node count
+hipError_t oct_build_scan(const float4* posm, int n, void* workspace, size_t sort_tmp_bytes, hipStream_t stream);
+// node records (n_nodes = counters[0], read by the host: the node array is sized from it)
+hipError_t oct_build_emit(int n, void* workspace, size_t sort_tmp_bytes, int n_nodes, OctNode* nodes, hipStream_t stream);
+hipError_t launch_oct_groups(const OctNode* nodes, int n_nodes, float theta, OctGroup* groups, hipStream_t stream);
+// one walk per wave over 64 bodies in key order.  kick_vel != nullptr: the walk ends the step (kick-drift and the 3-D kill box on its
+// own bodies, posm and kick_vel updated in place); else F = m * a of body i into forces[i]
+hipError_t launch_oct_walk(float4* posm, int n, const unsigned* order, const OctGroup* groups, float4* forces, float4* kick_vel,
+                           float dt, hipStream_t stream);
+
 struct ForceLaunch {
     int grid, block, jsplit, bpt, dim, variant;
 };

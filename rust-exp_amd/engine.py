@@ -39,6 +39,7 @@ NBX_OPT_BH_FOLD = 14
 NBX_OPT_BH_ASYNC = 15
 NBX_OPT_BH_WALK = 18
 NBX_OPT_BH_FUSE_KICK = 20
+NBX_OPT_BH_DIM = 22              # (21 is not an option)
 # (10-12 and 17 became enum nbx_stat in round 5; 16 and 19 -- measured losers -- were removed)
 
 NBX_STAT_BH_FALLBACKS = 0
@@ -209,6 +210,8 @@ def lib():
     L.nbx_bh_tree_dump.restype = i32
     L.nbx_bh_flat_dump.argtypes = [E, C.c_void_p, i32, i32]
     L.nbx_bh_flat_dump.restype = i32
+    L.nbx_bh_oct_dump.argtypes = [E, C.c_void_p, i32]
+    L.nbx_bh_oct_dump.restype = i32
     L.nbx_set_shard.argtypes = [E, i32, i32]
     L.nbx_set_shard.restype = i32
     L.nbx_get_slab.argtypes = [E, C.POINTER(i32), C.POINTER(i32)]
@@ -491,6 +494,10 @@ class NBodyEngine:
         tree bit for bit), 'exact' (roundings of exact sums) or 'auto' (reference up to 65 536 bodies)."""
         self.set_option(NBX_OPT_BH_FOLD, {"exact": 0, "reference": 1, "auto": -1}[how])
 
+    def set_bh_dim(self, dim):
+        """2 (default): Barnes-Hut on the quadtree of (x, y), z ignored; 3: the octree path (fast mode, one unsharded engine)."""
+        self.set_option(NBX_OPT_BH_DIM, dim)
+
     def set_draw_device(self, on=True):
         """True / False force the device / host draw; None = by size (the default)."""
         self.set_option(NBX_OPT_DRAW_DEVICE, -1 if on is None else (1 if on else 0))
@@ -514,6 +521,15 @@ class NBodyEngine:
         cnt = _check(self._L.nbx_bh_flat_dump(self._h, None, 0, mode))
         rows = np.zeros(max(cnt, 1), dt)
         cnt = _check(self._L.nbx_bh_flat_dump(self._h, _p(rows), cnt, mode))
+        return rows[:cnt]
+
+    def bh_oct_dump(self):
+        """The device-built octree of the current state as a structured array (px, py, pz, m, s, skip, interior, pad)."""
+        dt = np.dtype([("px", "<f4"), ("py", "<f4"), ("pz", "<f4"), ("m", "<f4"), ("s", "<f4"), ("skip", "<i4"),
+                       ("interior", "<i4"), ("pad", "<i4")])
+        cnt = _check(self._L.nbx_bh_oct_dump(self._h, None, 0))
+        rows = np.zeros(max(cnt, 1), dt)
+        cnt = _check(self._L.nbx_bh_oct_dump(self._h, _p(rows), cnt))
         return rows[:cnt]
 
     # sharding

@@ -28,7 +28,58 @@ def timed(fn, reps):
     return float(np.median(ts)), ts
 
 
+def split_steps(e, theta, dt, warmup=3, steps=20, profiled=10):
+    """Median ms/step with the profiler off (host clock around step + synchronise), then the build / walk split from HIP events."""
+    def step():
+        e.step_barnes_hut(theta, dt, 1); e.synchronize()
+
+    for _ in range(warmup):
+        step()
+    med, ts = timed(step, steps)
+    e.profile(True); e.profile_reset()
+    for _ in range(profiled):
+        step()
+    build_ms, _ = e.profile_read(rx.NBX_K_TREE_BUILD)
+    walk_ms, _ = e.profile_read(rx.NBX_K_BH_EVAL)
+    e.profile(False)
+    return {"ms_per_step_median": med * 1e3, "ms_per_step_min": min(ts) * 1e3, "ms_per_step_max": max(ts) * 1e3,
+            "build_kernels_ms": build_ms / profiled, "walk_kernels_ms": walk_ms / profiled, "steps_timed": steps}
+
+
+def main_dim3():
+    """--dim 3: the octree path (NBX_OPT_BH_DIM = 3) on the Plummer SPHERE, beside the quadtree path on the disc of the same
+    size and the all-pairs step at 262 144 bodies, all in one run."""
+    big = int(os.environ.get("BH_N", "1048576"))
+    out = {}
+    st = rx.plummer_sphere(big, dim=3)
+    e = rx.NBodyEngine(mode="fast")
+    e.set_bh_dim(3)
+    e.set_particles(st["px"], st["py"], st["vx"], st["vy"], st["m"], st["pz"], st["vz"])
+    out["bh_dim3_sphere"] = {"bodies": big, "theta": 0.5, "nodes": len(e.bh_oct_dump()), **split_steps(e, 0.5, 0.01)}
+    e.close()
+    st = rx.plummer_sphere(big, dim=2)
+    q = rx.NBodyEngine(mode="fast")
+    q.set_particles(st["px"], st["py"], st["vx"], st["vy"], st["m"])
+    out["bh_dim2_disc"] = {"bodies": big, "theta": 0.5, **split_steps(q, 0.5, 0.01)}
+    q.close()
+    small = int(os.environ.get("BRUTE_N", "262144"))
+    st = rx.plummer_sphere(small, dim=3)
+    b = rx.NBodyEngine(mode="fast")
+    b.set_particles(st["px"], st["py"], st["vx"], st["vy"], st["m"], st["pz"], st["vz"])
+
+    def brute():
+        b.step_brute_force(0.01); b.synchronize()
+
+    for _ in range(2):
+        brute()
+    med, ts = timed(brute, 5)
+    out["all_pairs_sphere"] = {"bodies": small, "ms_per_step_median": med * 1e3, "steps_timed": len(ts)}
+    print(json.dumps(out))
+
+
 def main():
+    if "--dim" in sys.argv and sys.argv[sys.argv.index("--dim") + 1:][:1] == ["3"]:
+        return main_dim3()
     out = {}
     big = int(os.environ.get("BH_N", "1048576"))
     st = rx.plummer_sphere(big, dim=2)
