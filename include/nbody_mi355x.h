@@ -307,6 +307,30 @@ int32_t nbx_synchronize(nbx_engine *e);
  * targets; fz may be NULL. theta == 0 -> all-pairs, else Barnes-Hut traversal. cap >= slab size. */
 int32_t nbx_forces(nbx_engine *e, float theta, int32_t cap, float *fx, float *fy, float *fz);
 
+/* The fp64 arbiter on the device: all-pairs, double precision, whatever the force mode, NBX_OPT_DIM or the source precision say:
+ *   F_i = m_i * sum_{j != i} m_j d / (|d|^2 + eps),   phi_i = sum_{j != i} m_j * 1/2 ln(|d|^2 + eps),   d = p_j - p_i in 3-D
+ * (z = 0 gives the planar law exactly), from the fp32 state widened exactly to fp64, eps = (double)0.0001f.  Targets = this engine's
+ * slab, sources = all n bodies; the live device state is read (a Barnes-Hut step still in flight is resolved first) and never
+ * modified.  Any output pointer may be NULL; phi == NULL skips the logarithm.  The pair j = i contributes nothing; distinct bodies
+ * at one position contribute zero force and m_j * 1/2 ln(eps).  Deterministic: fixed reduction orders, no floating-point atomics.
+ * Returns the slab size (cap >= slab size, else NBX_ERR_INVALID); NBX_ERR_NO_DEVICE without a GPU, NBX_ERR_STATE for a member of an
+ * nbx_group.  nbx_last_launch afterwards: variant 64, jsplit = the source split, bodies_per_thread = targets per lane. */
+int32_t nbx_forces_f64(nbx_engine *e, int32_t cap, double *fx, double *fy, double *fz, double *phi);
+
+enum nbx_conserved_id {
+    NBX_CONS_KINETIC = 0,    /* sum 1/2 m |v|^2 */
+    NBX_CONS_POTENTIAL = 1,  /* 1/2 sum_{i in slab} m_i phi_i: over all ranks, sum_{i<j} 1/2 m_i m_j ln(|d|^2 + eps) */
+    NBX_CONS_MASS = 2,
+    NBX_CONS_PX = 3, NBX_CONS_PY = 4, NBX_CONS_PZ = 5,      /* sum m v */
+    NBX_CONS_LX = 6, NBX_CONS_LY = 7, NBX_CONS_LZ = 8,      /* sum m (r x v) */
+    NBX_CONS_MRX = 9, NBX_CONS_MRY = 10, NBX_CONS_MRZ = 11, /* sum m r */
+    NBX_CONS_COUNT = 12
+};
+/* The conserved sums of the 1/r law in fp64, on the device, over this engine's slab targets (world == 1: the whole system; a
+ * sharded caller adds its ranks' arrays).  count must be NBX_CONS_COUNT (else NBX_ERR_INVALID); out[nbx_conserved_id].  Runs the
+ * sweep of nbx_forces_f64 with the potential; same statuses, same determinism, state untouched.  n == 0: all sums zero. */
+int32_t nbx_conserved(nbx_engine *e, int32_t count, double *out);
+
 int32_t nbx_draw(nbx_engine *e, int32_t w, int32_t h, uint32_t *fb);
 
 /* Host quadtree exactly as nbody.rs:388-415 builds it, dumped in pre-order (children UL,UR,LL,LR)

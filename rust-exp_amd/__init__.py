@@ -15,6 +15,19 @@ There is no CPU fallback anywhere in this package: without the HIP library the i
 without a GPU every step raises.
 """
 from .engine import (  # noqa: F401
+    NBX_CONS_COUNT,
+    NBX_CONS_KINETIC,
+    NBX_CONS_LX,
+    NBX_CONS_LY,
+    NBX_CONS_LZ,
+    NBX_CONS_MASS,
+    NBX_CONS_MRX,
+    NBX_CONS_MRY,
+    NBX_CONS_MRZ,
+    NBX_CONS_POTENTIAL,
+    NBX_CONS_PX,
+    NBX_CONS_PY,
+    NBX_CONS_PZ,
     NBX_ERR_INVALID,
     NBX_ERR_NO_DEVICE,
     NBX_ERR_STATE,

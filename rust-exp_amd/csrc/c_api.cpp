@@ -452,6 +452,19 @@ int32_t nbx_forces(nbx_engine* e, float theta, int32_t cap, float* fx, float* fy
     return slab;
 }
 
+// the fp64 all-pairs sweep (K7: engine_diag.cpp, diag64.hip)
+int32_t nbx_forces_f64(nbx_engine* e, int32_t cap, double* fx, double* fy, double* fz, double* phi)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return forces_f64(e, cap, fx, fy, fz, phi);
+}
+
+int32_t nbx_conserved(nbx_engine* e, int32_t count, double* out)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return conserved_f64(e, count, out);
+}
+
 // device splat (draw.hip): needs the whole state on this GPU (unsharded) and a live device
 static int draw_on_device(nbx_engine* e, int32_t w, int32_t h, uint32_t* fb)
 {

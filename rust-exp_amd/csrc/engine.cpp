@@ -394,6 +394,10 @@ void free_device(nbx_engine* e)
     if (e->d_guard) (void)hipFree(e->d_guard);
     if (e->d_exc_idx) (void)hipFree(e->d_exc_idx);
     if (e->d_src4) (void)hipFree(e->d_src4);
+    if (e->d_src64) (void)hipFree(e->d_src64);
+    if (e->d_part64) (void)hipFree(e->d_part64);
+    if (e->d_out64) (void)hipFree(e->d_out64);
+    if (e->d_cons64) (void)hipFree(e->d_cons64);
     if (e->d_exc_rec) (void)hipFree(e->d_exc_rec);
     if (e->d_tree_ws) (void)hipFree(e->d_tree_ws);
     if (e->d_slab_ws) (void)hipFree(e->d_slab_ws);

@@ -198,6 +198,15 @@ struct nbx_engine {
     int source_half = 0;
     float4* d_src4 = nullptr;      // the fp16 source copy widened to float4, rewritten before every wave-split sweep (K4)
     size_t src4_cap = 0;
+    // K7, the fp64 sweep of nbx_forces_f64 / nbx_conserved (engine_diag.cpp): workspaces only, rewritten by every call
+    double4* d_src64 = nullptr;    // posm[0..n) widened to double4
+    size_t src64_cap = 0;
+    double4* d_part64 = nullptr;   // [split][stride] partial sums
+    size_t part64_cap = 0;
+    double4* d_out64 = nullptr;    // (Fx, Fy, Fz, phi) per slab target
+    size_t out64_cap = 0;
+    double* d_cons64 = nullptr;    // the 12 sums, then the workgroups' partials
+    size_t cons64_cap = 0;
 
     // options
     int force_mode = 0, jsplit = 0, bpt = 0, dim_opt = 0, profile = 0, variant = -1, strict_kernel = 0;
@@ -431,6 +440,9 @@ int bh3_refusal(const nbx_engine* e);   // NBX_OK, or the status of a configurat
 int step_bh3(nbx_engine* e, float theta, float dt);
 int forces_bh3(nbx_engine* e, float theta, float* fx, float* fy, float* fz);
 int oct_dump(nbx_engine* e, void* rows, int cap);
+// engine_diag.cpp: the fp64 all-pairs sweep (K7) on the live device state, which it never modifies
+int forces_f64(nbx_engine* e, int cap, double* fx, double* fy, double* fz, double* phi);
+int conserved_f64(nbx_engine* e, int count, double* out);
 int resolve_pending(nbx_engine* e);   // the verdicts of the speculatively enqueued Barnes-Hut steps, oldest first (no-op when none)
 void free_device(nbx_engine* e);
 uint64_t entropy_seed();

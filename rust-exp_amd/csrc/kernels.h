@@ -160,6 +160,28 @@ hipError_t launch_reduce_forces(const float4* posm, int lo, int n_targets, const
                                 MassExceptions exc = MassExceptions{nullptr, nullptr, 0, 3},
                                 SelfImage si = SelfImage{nullptr, 0.0f, 3});
 
+// ---- K7 (diag64.hip): the fp64 all-pairs sweep behind nbx_forces_f64 / nbx_conserved ----
+#ifndef NBX_SWEEP64_T
+#define NBX_SWEEP64_T 4   // (1 and 2 also build: the A/B of docs/rounds/r08.md compiled diag64.hip with -DNBX_SWEEP64_T=...)
+#endif
+constexpr int kSweep64Targets = NBX_SWEEP64_T;   // T, targets per lane; a workgroup = 4 waves sharing 64 * T targets
+// src64[i] = (double4)posm[i] for i < n: the sources as 32-byte records, one 8-dword scalar load each
+hipError_t launch_widen64(const float4* posm, double4* src64, int n, hipStream_t stream);
+// the source split that fills `cu_count` CUs: at least one, at most n / 64 (every wave keeps 16 sources or more)
+int sweep64_split(int n_targets, int n_sources, int cu_count);
+int sweep64_stride(int n_targets);   // records per partial slab: the targets rounded up to whole workgroups
+// partial[s][t] = (sum m_j d / (|d|^2 + eps), sum m_j ln(|d|^2 + eps)) over the s-th of `split` source ranges, for targets
+// posm[lo + t], t < n_targets; pot = false leaves the logarithm out (.w = 0)
+hipError_t launch_sweep64(const float4* posm, const double4* src64, int lo, int n_targets, int n_sources, int split, bool pot,
+                          double4* partial, hipStream_t stream, ForceLaunch* info);
+// out[t] = (m_t * sum of the partials' xyz in ascending split order, 1/2 * sum of their w)
+hipError_t launch_reduce64(const float4* posm, int lo, int n_targets, const double4* partial, int split, double4* out,
+                           hipStream_t stream);
+// the 12 sums of nbx_conserved_id over the slab into sums[0..12); workspace: conserved64_workspace(n_targets) doubles
+size_t conserved64_workspace(int n_targets);
+hipError_t launch_conserved64(const float4* posm, int lo, int n_targets, const float4* vel, const double4* out, double* workspace,
+                              double* sums, hipStream_t stream);
+
 // strict (bit-exact) pair: ascending j per target, IEEE divide, no contraction. 2-D.
 // kernel: 16 or 8 = workgroups of that many waves per 64 targets (term producers + one summing wave), 1 = one thread per body,
 // anything else = by size (strict_kernel_choice); info->variant = -(kernel). Results are bit-identical whichever runs.

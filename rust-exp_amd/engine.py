@@ -62,6 +62,15 @@ NBX_K_BH_EVAL = 2
 NBX_K_EXCHANGE = 3
 NBX_K_TREE_BUILD = 4
 
+# nbx_conserved_id: the slots of nbx_conserved's array
+NBX_CONS_KINETIC = 0
+NBX_CONS_POTENTIAL = 1
+NBX_CONS_MASS = 2
+NBX_CONS_PX, NBX_CONS_PY, NBX_CONS_PZ = 3, 4, 5
+NBX_CONS_LX, NBX_CONS_LY, NBX_CONS_LZ = 6, 7, 8
+NBX_CONS_MRX, NBX_CONS_MRY, NBX_CONS_MRZ = 9, 10, 11
+NBX_CONS_COUNT = 12
+
 
 class NBodyError(RuntimeError):
     def __init__(self, code, text):
@@ -204,6 +213,10 @@ def lib():
     L.nbx_synchronize.restype = i32
     L.nbx_forces.argtypes = [E, C.c_float, i32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.nbx_forces.restype = i32
+    L.nbx_forces_f64.argtypes = [E, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.nbx_forces_f64.restype = i32
+    L.nbx_conserved.argtypes = [E, i32, C.c_void_p]
+    L.nbx_conserved.restype = i32
     L.nbx_draw.argtypes = [E, i32, i32, C.c_void_p]
     L.nbx_draw.restype = i32
     L.nbx_bh_tree_dump.argtypes = [E, C.c_void_p, i32]
@@ -483,6 +496,23 @@ class NBodyEngine:
         fz = np.zeros(hi - lo, np.float32)
         _check(self._L.nbx_forces(self._h, theta, hi - lo, _p(fx), _p(fy), _p(fz)))
         return fx, fy, fz
+
+    def forces_f64(self, potential=True):
+        """The fp64 arbiter on the device (nbx_forces_f64): all-pairs F_i and phi_i = sum_j m_j 1/2 ln(|d|^2 + eps) of this
+        engine's slab as float64 arrays fx, fy, fz, phi; potential=False skips the logarithm and returns phi = None."""
+        lo, hi = self.slab()
+        fx, fy, fz = (np.zeros(hi - lo, np.float64) for _ in range(3))
+        phi = np.zeros(hi - lo, np.float64) if potential else None
+        _check(self._L.nbx_forces_f64(self._h, hi - lo, _p(fx), _p(fy), _p(fz), _p(phi) if potential else None))
+        return fx, fy, fz, phi
+
+    def conserved(self, count=NBX_CONS_COUNT):
+        """The conserved sums over this engine's slab in fp64 (nbx_conserved; a sharded caller adds its ranks' values)."""
+        out = np.zeros(max(count, NBX_CONS_COUNT), np.float64)
+        _check(self._L.nbx_conserved(self._h, count, _p(out)))
+        return {"kinetic": float(out[NBX_CONS_KINETIC]), "potential": float(out[NBX_CONS_POTENTIAL]),
+                "mass": float(out[NBX_CONS_MASS]), "momentum": out[NBX_CONS_PX:NBX_CONS_PX + 3].copy(),
+                "angular_momentum": out[NBX_CONS_LX:NBX_CONS_LX + 3].copy(), "mass_moment": out[NBX_CONS_MRX:NBX_CONS_MRX + 3].copy()}
 
     def set_bh_tree(self, where):
         """'host' (reference-faithful insertion build), 'device' (bh_build.hip) or 'auto' (default: device in the fast
