@@ -331,6 +331,29 @@ enum nbx_conserved_id {
  * sweep of nbx_forces_f64 with the potential; same statuses, same determinism, state untouched.  n == 0: all sums zero. */
 int32_t nbx_conserved(nbx_engine *e, int32_t count, double *out);
 
+/* The 4th-order Hermite step (Makino & Aarseth 1992, PEC) on the all-pairs law and its time derivative, in fp32 on the device:
+ *   a_i = sum_j m_j d / s,   j_i = sum_j m_j ( w / s - 2 (d.w) d / s^2 ),   d = p_j - p_i, w = v_j - v_i, s = |d|^2 + eps
+ * (3-D; z = 0 gives the planar law exactly; NBX_OPT_DIM chooses the sweep as for nbx_step_brute_force).  One step of size dt:
+ *   predict   xp = x + v dt + a0 dt^2/2 + j0 dt^3/6,   vp = v + a0 dt + j0 dt^2/2
+ *   evaluate  (a1, j1) at (xp, vp): one sweep that computes both
+ *   correct   v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12,   x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12
+ * and (a1, j1) is kept on the device as the next step's (a0, j0).  Anything else that can change positions, velocities or masses
+ * -- new particles, nbx_load, any other step, nbx_positions_device, a change of NBX_OPT_DIM -- discards the kept pair, and the
+ * next Hermite step first evaluates it at the current state (one more sweep).  No velocity kill box.  Asynchronous on the engine's
+ * stream, like the other steps; deterministic (fixed reduction orders, no atomics).  NBX_OPT_JSPLIT sets the source split (0 =
+ * by size).  nbx_last_launch afterwards: variant 40, jsplit = the source split, bodies_per_thread = targets per lane.
+ * NBX_ERR_NO_DEVICE without a GPU; NBX_ERR_STATE for a sharded engine (world > 1: the other slabs' velocities are elsewhere), a
+ * member of an nbx_group, the bit-exact force mode and NBX_OPT_SOURCE_PRECISION = 16; the state is untouched then. */
+int32_t nbx_step_hermite(nbx_engine *e, float dt);
+/* a_i and j_i (above; accelerations, not forces) of the current state, evaluated afresh by the same sweep.  State untouched; any
+ * output pointer may be NULL; cap >= n; returns n.  The pair j = i contributes exact zeros; distinct bodies at one position
+ * contribute zero acceleration and the finite jerk m_j w / eps.  Leaves the evaluated pair as the kept (a0, j0): a Hermite step
+ * that follows starts from it.  Statuses as nbx_step_hermite. */
+int32_t nbx_acc_jerk(nbx_engine *e, int32_t cap, float *ax, float *ay, float *az, float *jx, float *jy, float *jz);
+/* The shared Aarseth-style step *dt_out = eta * min_i |a_i| / |j_i| over the kept (a0, j0), reduced on the device (evaluated
+ * first if there is no valid pair).  Bodies with |j_i| = 0 are skipped; none left (or n == 0): +inf.  Statuses as above. */
+int32_t nbx_hermite_timestep(nbx_engine *e, float eta, float *dt_out);
+
 int32_t nbx_draw(nbx_engine *e, int32_t w, int32_t h, uint32_t *fb);
 
 /* Host quadtree exactly as nbody.rs:388-415 builds it, dumped in pre-order (children UL,UR,LL,LR)

@@ -88,6 +88,7 @@ int32_t nbx_set_option(nbx_engine* e, int32_t option, int64_t value)
         case NBX_OPT_DIM:
             if (value != 0 && value != 2 && value != 3) return fail(NBX_ERR_INVALID, "dim must be 0,2,3");
             e->dim_opt = (int)value;
+            e->hermite_valid = false;   // (the kept (a0, j0) of a Hermite step came from a sweep of the old dimension)
             return NBX_OK;
         case NBX_OPT_PROFILE:
             e->profile = value ? 1 : 0;
@@ -463,6 +464,25 @@ int32_t nbx_conserved(nbx_engine* e, int32_t count, double* out)
 {
     if (!e) return fail(NBX_ERR_INVALID, "null engine");
     return conserved_f64(e, count, out);
+}
+
+// the 4th-order Hermite step and its acceleration + jerk sweep (K8: engine_hermite.cpp, hermite.hip)
+int32_t nbx_step_hermite(nbx_engine* e, float dt)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return step_hermite(e, dt);
+}
+
+int32_t nbx_acc_jerk(nbx_engine* e, int32_t cap, float* ax, float* ay, float* az, float* jx, float* jy, float* jz)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return acc_jerk(e, cap, ax, ay, az, jx, jy, jz);
+}
+
+int32_t nbx_hermite_timestep(nbx_engine* e, float eta, float* dt_out)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return hermite_timestep(e, eta, dt_out);
 }
 
 // device splat (draw.hip): needs the whole state on this GPU (unsharded) and a live device

@@ -398,6 +398,10 @@ void free_device(nbx_engine* e)
     if (e->d_part64) (void)hipFree(e->d_part64);
     if (e->d_out64) (void)hipFree(e->d_out64);
     if (e->d_cons64) (void)hipFree(e->d_cons64);
+    if (e->d_hsrc) (void)hipFree(e->d_hsrc);
+    if (e->d_hpart) (void)hipFree(e->d_hpart);
+    if (e->d_hkept) (void)hipFree(e->d_hkept);
+    if (e->d_hdt) (void)hipFree(e->d_hdt);
     if (e->d_exc_rec) (void)hipFree(e->d_exc_rec);
     if (e->d_tree_ws) (void)hipFree(e->d_tree_ws);
     if (e->d_slab_ws) (void)hipFree(e->d_slab_ws);
@@ -436,6 +440,7 @@ void after_host_state_change(nbx_engine* e)
         e->pending[0].active = e->pending[1].active = false;
     }
     e->n = e->host.n();
+    e->hermite_valid = false;   // new bodies: the kept (a0, j0) belong to the old ones
     e->reset_backoff();
     compute_slab(e);
     e->host_pos_valid = e->host_vel_valid = true;

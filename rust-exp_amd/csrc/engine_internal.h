@@ -73,7 +73,7 @@ struct nbx_engine {
     bool sorted_pos_valid = false;      // ... and whether they still ARE the current positions in that order: set by the launch of a
                                         // fused walk + kick-drift, taken back by everything else that moves bodies on the device or
                                         // replaces the order (positions_moved()); never with a bound positions buffer or world > 1
-    void positions_moved() { sorted_pos_valid = false; }
+    void positions_moved() { sorted_pos_valid = false; hermite_valid = false; }   // (... and the kept (a0, j0) of the Hermite step)
     const float4* sorted_positions() const { return (sorted_pos_valid && world == 1 && !posm_external && sort_warm_n == n) ? d_sorted_pos : nullptr; }
     int sort_warm_n = 0;                // > 0: the tree workspace holds the sorted order of this many bodies as of the last build /
                                         // spatial order of THIS state (one step old at most): the next sort starts from it (bh_build.hip,
@@ -207,6 +207,19 @@ struct nbx_engine {
     size_t out64_cap = 0;
     double* d_cons64 = nullptr;    // the 12 sums, then the workgroups' partials
     size_t cons64_cap = 0;
+    // K8, the Hermite step (engine_hermite.cpp): workspaces, and the one piece of state the integrator keeps between steps
+    nbx::HermiteSrc* d_hsrc = nullptr;    // the sweep's source records: every body, predicted (n_pad records)
+    size_t hsrc_cap = 0;
+    nbx::HermiteAJ* d_hpart = nullptr;    // [jsplit][stride] partial (a, j)
+    size_t hpart_cap = 0;
+    nbx::HermiteAJ* d_hkept = nullptr;    // (a0, j0) per slab body
+    size_t hkept_cap = 0;
+    float* d_hdt = nullptr;               // the time-step reduction's result, then the workgroups' minima
+    size_t hdt_cap = 0;
+    bool hermite_valid = false;           // d_hkept holds what the next Hermite step may start from: set by a Hermite step and by
+                                          // nbx_acc_jerk, taken back by everything else that can change positions, velocities or
+                                          // masses (positions_moved(), after_host_state_change) or the sweep's dimension
+    int hermite_dim = 0;                  // ... and the DIM the sweep that produced them ran with
 
     // options
     int force_mode = 0, jsplit = 0, bpt = 0, dim_opt = 0, profile = 0, variant = -1, strict_kernel = 0;
@@ -443,6 +456,10 @@ int oct_dump(nbx_engine* e, void* rows, int cap);
 // engine_diag.cpp: the fp64 all-pairs sweep (K7) on the live device state, which it never modifies
 int forces_f64(nbx_engine* e, int cap, double* fx, double* fy, double* fz, double* phi);
 int conserved_f64(nbx_engine* e, int count, double* out);
+// engine_hermite.cpp: the 4th-order Hermite step around the acceleration + jerk sweep (K8)
+int step_hermite(nbx_engine* e, float dt);
+int acc_jerk(nbx_engine* e, int cap, float* ax, float* ay, float* az, float* jx, float* jy, float* jz);
+int hermite_timestep(nbx_engine* e, float eta, float* dt_out);
 int resolve_pending(nbx_engine* e);   // the verdicts of the speculatively enqueued Barnes-Hut steps, oldest first (no-op when none)
 void free_device(nbx_engine* e);
 uint64_t entropy_seed();

@@ -182,6 +182,39 @@ size_t conserved64_workspace(int n_targets);
 hipError_t launch_conserved64(const float4* posm, int lo, int n_targets, const float4* vel, const double4* out, double* workspace,
                               double* sums, hipStream_t stream);
 
+// ---- K8 (hermite.hip): the acceleration + jerk sweep behind nbx_step_hermite / nbx_acc_jerk / nbx_hermite_timestep ----
+#ifndef NBX_HERMITE_T
+#define NBX_HERMITE_T 2   // (1 and 4 also build: the A/B of docs/rounds/r09.md compiled hermite.hip with -DNBX_HERMITE_T=...)
+#endif
+constexpr int kHermiteTargets = NBX_HERMITE_T;   // T, targets per lane; a workgroup = 4 waves sharing 64 * T targets
+// source record of the sweep: the (predicted) body, 32 bytes = one 8-dword scalar load
+struct alignas(32) HermiteSrc {
+    float x, y, z, m, vx, vy, vz, pad;
+};
+// (ax, ay, az, 0), (jx, jy, jz, 0): a partial sum of the sweep, or a body's kept (a0, j0)
+struct alignas(32) HermiteAJ {
+    float4 a, j;
+};
+// src[i] = body i of posm / vel for i < n, advanced by dt along its kept (a0, j0) when predict (else as it is: kept is not read);
+// zero records for n <= i < n_pad.  Unsharded engines only: vel holds all n bodies
+hipError_t launch_hermite_predict(const float4* posm, const float4* vel, const HermiteAJ* kept, int n, int n_pad, bool predict,
+                                  float dt, HermiteSrc* src, hipStream_t stream);
+int hermite_stride(int n_targets);   // records per partial slab: the targets rounded up to whole workgroups
+// the source split for auto: enough workgroups to fill `cu_count` CUs, every wave keeping a whole tile of sources
+int hermite_split(int n_targets, int tiles_total, int cu_count);
+// partial[s][t] = (a, j) of target src[lo + t], t < n_targets, over the s-th of `jsplit` ranges of the tiles_total * kTile sources;
+// 1 <= jsplit <= tiles_total.  info->variant = 40, bpt = T
+hipError_t launch_hermite_sweep(const HermiteSrc* src, int lo, int n_targets, int tiles_total, int jsplit, int dim,
+                                HermiteAJ* partial, hipStream_t stream, ForceLaunch* info);
+// partials in ascending order = (a1, j1); the corrector on posm[lo + i], vel[i] with kept[i] = (a0, j0); kept[i] <- (a1, j1)
+hipError_t launch_hermite_correct(float4* posm, int lo, int n_targets, float4* vel, const HermiteAJ* partial, int jsplit,
+                                  HermiteAJ* kept, float dt, hipStream_t stream);
+// kept[i] <- the partials in ascending order; nothing else is written
+hipError_t launch_hermite_keep(int n_targets, const HermiteAJ* partial, int jsplit, HermiteAJ* kept, hipStream_t stream);
+// workspace[0] = min_i |a_i| / |j_i| over kept[0..n_targets) (|j_i| = 0 skipped; +inf if none); hermite_dtmin_workspace() floats
+size_t hermite_dtmin_workspace(int n_targets);
+hipError_t launch_hermite_dtmin(const HermiteAJ* kept, int n_targets, float* workspace, hipStream_t stream);
+
 // strict (bit-exact) pair: ascending j per target, IEEE divide, no contraction. 2-D.
 // kernel: 16 or 8 = workgroups of that many waves per 64 targets (term producers + one summing wave), 1 = one thread per body,
 // anything else = by size (strict_kernel_choice); info->variant = -(kernel). Results are bit-identical whichever runs.

@@ -217,6 +217,12 @@ def lib():
     L.nbx_forces_f64.restype = i32
     L.nbx_conserved.argtypes = [E, i32, C.c_void_p]
     L.nbx_conserved.restype = i32
+    L.nbx_step_hermite.argtypes = [E, C.c_float]
+    L.nbx_step_hermite.restype = i32
+    L.nbx_acc_jerk.argtypes = [E, i32] + [C.c_void_p] * 6
+    L.nbx_acc_jerk.restype = i32
+    L.nbx_hermite_timestep.argtypes = [E, C.c_float, C.POINTER(C.c_float)]
+    L.nbx_hermite_timestep.restype = i32
     L.nbx_draw.argtypes = [E, i32, i32, C.c_void_p]
     L.nbx_draw.restype = i32
     L.nbx_bh_tree_dump.argtypes = [E, C.c_void_p, i32]
@@ -513,6 +519,23 @@ class NBodyEngine:
         return {"kinetic": float(out[NBX_CONS_KINETIC]), "potential": float(out[NBX_CONS_POTENTIAL]),
                 "mass": float(out[NBX_CONS_MASS]), "momentum": out[NBX_CONS_PX:NBX_CONS_PX + 3].copy(),
                 "angular_momentum": out[NBX_CONS_LX:NBX_CONS_LX + 3].copy(), "mass_moment": out[NBX_CONS_MRX:NBX_CONS_MRX + 3].copy()}
+
+    def step_hermite(self, dt):
+        """One 4th-order Hermite step (nbx_step_hermite): predict, one acceleration + jerk sweep, correct."""
+        _check(self._L.nbx_step_hermite(self._h, dt))
+
+    def acc_jerk(self):
+        """Accelerations and jerks of the current state as six float32 arrays ax, ay, az, jx, jy, jz (nbx_acc_jerk)."""
+        n = self.num_particles()
+        out = [np.zeros(n, np.float32) for _ in range(6)]
+        _check(self._L.nbx_acc_jerk(self._h, n, *[_p(a) for a in out]))
+        return tuple(out)
+
+    def hermite_timestep(self, eta):
+        """eta * min_i |a_i| / |j_i| (nbx_hermite_timestep): the shared Aarseth-style step, reduced on the device."""
+        dt = C.c_float()
+        _check(self._L.nbx_hermite_timestep(self._h, eta, C.byref(dt)))
+        return float(dt.value)
 
     def set_bh_tree(self, where):
         """'host' (reference-faithful insertion build), 'device' (bh_build.hip) or 'auto' (default: device in the fast
