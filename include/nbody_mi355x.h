@@ -214,11 +214,13 @@ enum nbx_stat {
     NBX_STAT_BH_CHAIN_MERGED = 6,  /* exact-sum device build (round 6): bodies the last accepted build merged into another body's leaf
                                     * by replaying chains of bodies within EPS in arrival order (nbody.rs:249-260; rounds 2-5 merged
                                     * pairs only and handed crowded systems to the host build) */
-    NBX_STAT_BH_CHAIN_APPROX = 7   /* ... and what of that build was approximate: bodies of blobs that end at a cut of a chain of more than 60
+    NBX_STAT_BH_CHAIN_APPROX = 7,  /* ... and what of that build was approximate: bodies of blobs that end at a cut of a chain of more than 60
                                     * linked bodies (such chains are replayed in pieces) + merges decided with the search for an earlier arrival deeper in
                                     * the newcomer's path cut short (more than 256 sorted neighbours share the cell: taken as merges).
                                     * At most max(16, n/2000) in a build that was accepted: beyond that the step goes to the host build
                                     * (NBX_STAT_BH_REFUSAL 0x20000) */
+    NBX_STAT_HERMITE_BLOCK_STEPS = 8, /* block steps of the last nbx_step_hermite_block macro-step */
+    NBX_STAT_HERMITE_BLOCK_EVALS = 9  /* ... and the sum of their block sizes: body evaluations (n per shared step) */
 };
 
 enum nbx_kernel_id {
@@ -353,6 +355,34 @@ int32_t nbx_acc_jerk(nbx_engine *e, int32_t cap, float *ax, float *ay, float *az
 /* The shared Aarseth-style step *dt_out = eta * min_i |a_i| / |j_i| over the kept (a0, j0), reduced on the device (evaluated
  * first if there is no valid pair).  Bodies with |j_i| = 0 are skipped; none left (or n == 0): +inf.  Statuses as above. */
 int32_t nbx_hermite_timestep(nbx_engine *e, float eta, float *dt_out);
+
+/* Individual, hierarchical ("block") time steps for the same scheme.  Every body has its own step dt_max 2^-level, level 0 ..
+ * NBX_HERMITE_MAX_LEVEL; time is kept in integer ticks of dt_max 2^-20, so "due" is an exact compare.  The call advances EVERY body
+ * by exactly dt_max through block steps: at each block time only the bodies that are due get a new (a1, j1) -- evaluated against
+ * all bodies predicted to that time over their own spans -- and are corrected; the last block of a macro-step holds every body.
+ * eta > 0: after each update a body's level follows dt_req = eta |a1| / |j1| (deeper while dt(level) > dt_req; one level up if
+ * 2 dt(level) <= dt_req and the block time is a multiple of the doubled step).  The full Aarseth criterion, which needs higher
+ * derivatives from differences that cancel in fp32, is not used.  eta <= 0: levels stay what they are (all 0 if none were set).
+ * Without a valid block state the call first evaluates (a0, j0) as nbx_step_hermite does and makes the levels from eta.  Whatever
+ * discards the kept pair discards the levels; so do a shared nbx_step_hermite and a dt_max other than the one they were made for.
+ * With every level 0 and eta <= 0 a macro-step is nbx_step_hermite(dt_max) bit for bit.  One 8-byte synchronous read per block
+ * step.  nbx_last_launch afterwards: variant 41 (the last block's sweep), bodies_per_thread = 1 or 2.  Statuses as
+ * nbx_step_hermite; dt_max <= 0 or not finite: NBX_ERR_INVALID. */
+#define NBX_HERMITE_MAX_LEVEL 20
+int32_t nbx_step_hermite_block(nbx_engine *e, float dt_max, float eta);
+/* Prescribes / reads the levels (n = the particle count).  Setting evaluates (a0, j0) if there is no valid pair and makes the block
+ * state valid for whatever dt_max the next nbx_step_hermite_block names; a level outside 0 .. NBX_HERMITE_MAX_LEVEL is
+ * NBX_ERR_INVALID.  Reading returns n, or NBX_ERR_STATE when there are no valid levels. */
+int32_t nbx_hermite_block_set_levels(nbx_engine *e, const int32_t *levels, int32_t n);
+int32_t nbx_hermite_block_levels(nbx_engine *e, int32_t cap, int32_t *out);
+/* The kept (a0, j0) as they are, without a new evaluation: after a step, those of the last predicted state.  Returns n;
+ * NBX_ERR_STATE when there is no valid pair. */
+int32_t nbx_hermite_kept(nbx_engine *e, int32_t cap, float *ax, float *ay, float *az, float *jx, float *jy, float *jz);
+/* a_i and j_i of the `count` listed bodies at the current state, by the block step's sweep over a list of targets: each row is,
+ * for the same source split, nbx_acc_jerk's row of that body bit for bit, whatever its place in the list.  State and kept pair
+ * untouched; any output pointer may be NULL; returns count.  An index outside [0, n): NBX_ERR_INVALID. */
+int32_t nbx_acc_jerk_subset(nbx_engine *e, const int32_t *idx, int32_t count, float *ax, float *ay, float *az, float *jx, float *jy,
+                            float *jz);
 
 int32_t nbx_draw(nbx_engine *e, int32_t w, int32_t h, uint32_t *fb);
 

@@ -200,6 +200,8 @@ int64_t nbx_get_stat(const nbx_engine* e, int32_t stat)
         case NBX_STAT_BH_LAST_TREE: return e->bh_last_tree_device;
         case NBX_STAT_BH_REFUSAL: return e->bh_last_refusal;
         case NBX_STAT_DRAW_AMBIGUOUS: return e->draw_ambiguous;
+        case NBX_STAT_HERMITE_BLOCK_STEPS: return e->hblock_steps;
+        case NBX_STAT_HERMITE_BLOCK_EVALS: return e->hblock_evals;
         default: return INT64_MIN;
     }
 }
@@ -483,6 +485,38 @@ int32_t nbx_hermite_timestep(nbx_engine* e, float eta, float* dt_out)
 {
     if (!e) return fail(NBX_ERR_INVALID, "null engine");
     return hermite_timestep(e, eta, dt_out);
+}
+
+// Hermite block time steps and the subset sweep (K9: engine_hermite_block.cpp, hermite_block.hip)
+int32_t nbx_step_hermite_block(nbx_engine* e, float dt_max, float eta)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return step_hermite_block(e, dt_max, eta);
+}
+
+int32_t nbx_hermite_block_set_levels(nbx_engine* e, const int32_t* levels, int32_t n)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return hermite_block_set_levels(e, levels, n);
+}
+
+int32_t nbx_hermite_block_levels(nbx_engine* e, int32_t cap, int32_t* out)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return hermite_block_levels(e, cap, out);
+}
+
+int32_t nbx_hermite_kept(nbx_engine* e, int32_t cap, float* ax, float* ay, float* az, float* jx, float* jy, float* jz)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return hermite_kept(e, cap, ax, ay, az, jx, jy, jz);
+}
+
+int32_t nbx_acc_jerk_subset(nbx_engine* e, const int32_t* idx, int32_t count, float* ax, float* ay, float* az, float* jx, float* jy,
+                            float* jz)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return acc_jerk_subset(e, idx, count, ax, ay, az, jx, jy, jz);
 }
 
 // device splat (draw.hip): needs the whole state on this GPU (unsharded) and a live device

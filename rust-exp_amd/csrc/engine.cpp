@@ -402,6 +402,11 @@ void free_device(nbx_engine* e)
     if (e->d_hpart) (void)hipFree(e->d_hpart);
     if (e->d_hkept) (void)hipFree(e->d_hkept);
     if (e->d_hdt) (void)hipFree(e->d_hdt);
+    if (e->d_hbt) (void)hipFree(e->d_hbt);
+    if (e->d_hblist) (void)hipFree(e->d_hblist);
+    if (e->d_hbws) (void)hipFree(e->d_hbws);
+    if (e->d_hbout) (void)hipFree(e->d_hbout);
+    if (e->h_hbhead) (void)hipHostFree(e->h_hbhead);
     if (e->d_exc_rec) (void)hipFree(e->d_exc_rec);
     if (e->d_tree_ws) (void)hipFree(e->d_tree_ws);
     if (e->d_slab_ws) (void)hipFree(e->d_slab_ws);

@@ -10,11 +10,11 @@
 
 namespace nbxi {
 
-static int sweep_dim(const nbx_engine* e) { return e->dim_opt ? e->dim_opt : (e->any_z ? 3 : 2); }   // as choose_launch
+int hermite_sweep_dim(const nbx_engine* e) { return e->dim_opt ? e->dim_opt : (e->any_z ? 3 : 2); }   // as choose_launch
 
 // what the three entry points check first: a device, then a configuration the sweep serves; the upload resolves a Barnes-Hut
 // step still in flight (ensure_device)
-static int hermite_ready(nbx_engine* e)
+int hermite_ready(nbx_engine* e)
 {
     int rc = ensure_device(e);
     if (rc != NBX_OK) return rc;
@@ -28,7 +28,7 @@ static int hermite_ready(nbx_engine* e)
 // predict (dt along the kept pair, or the bodies as they are) and sweep: leaves the partial (a, j) in e->d_hpart
 static int predict_and_sweep(nbx_engine* e, bool predict, float dt)
 {
-    const int n = e->n, tiles_total = e->n_pad / kTile, dim = sweep_dim(e);
+    const int n = e->n, tiles_total = e->n_pad / kTile, dim = hermite_sweep_dim(e);
     int split = e->jsplit > 0 ? e->jsplit : nbx::hermite_split(n, tiles_total, e->cu_count);
     split = std::max(1, std::min(split, tiles_total));
     int rc = grow(&e->d_hsrc, &e->hsrc_cap, (size_t)e->n_pad);
@@ -47,8 +47,9 @@ static int predict_and_sweep(nbx_engine* e, bool predict, float dt)
 }
 
 // (a0, j0) of the current state into e->d_hkept
-static int evaluate_kept(nbx_engine* e)
+int hermite_evaluate_kept(nbx_engine* e)
 {
+    if (!hermite_kept_usable(e)) e->hblock_valid = false;   // (the levels of a block step belong to the pair that is gone)
     e->hermite_valid = false;
     int rc = predict_and_sweep(e, false, 0.0f);
     if (rc != NBX_OK) return rc;
@@ -58,18 +59,19 @@ static int evaluate_kept(nbx_engine* e)
     return NBX_OK;
 }
 
-static bool kept_usable(const nbx_engine* e) { return e->hermite_valid && e->hermite_dim == sweep_dim(e) && e->d_hkept; }
+bool hermite_kept_usable(const nbx_engine* e) { return e->hermite_valid && e->hermite_dim == hermite_sweep_dim(e) && e->d_hkept; }
 
 int step_hermite(nbx_engine* e, float dt)
 {
     int rc = hermite_ready(e);   // (an upload of new host state takes the flag back: positions_moved())
     if (rc != NBX_OK) return rc;
     if (e->n == 0) return NBX_OK;
-    if (!kept_usable(e)) {
-        rc = evaluate_kept(e);
+    if (!hermite_kept_usable(e)) {
+        rc = hermite_evaluate_kept(e);
         if (rc != NBX_OK) return rc;
     }
     e->hermite_valid = false;   // until the corrector is enqueued
+    e->hblock_valid = false;    // (a shared step leaves the bodies at one time but its kept pair says nothing about levels)
     rc = predict_and_sweep(e, true, dt);
     if (rc != NBX_OK) return rc;
     {
@@ -95,7 +97,7 @@ int acc_jerk(nbx_engine* e, int cap, float* ax, float* ay, float* az, float* jx,
     if (cap < n) return fail(NBX_ERR_INVALID, "capacity %d < particle count %d", cap, n);
     if (n == 0) return 0;
     // always a fresh evaluation: after a Hermite step the kept pair is that of the PREDICTED state, not of the current one
-    rc = evaluate_kept(e);
+    rc = hermite_evaluate_kept(e);
     if (rc != NBX_OK) return rc;
     std::vector<nbx::HermiteAJ> tmp((size_t)n);
     HIP_TRY(hipMemcpyAsync(tmp.data(), e->d_hkept, sizeof(nbx::HermiteAJ) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
@@ -118,8 +120,8 @@ int hermite_timestep(nbx_engine* e, float eta, float* dt_out)
     if (!dt_out) return fail(NBX_ERR_INVALID, "null dt_out");
     float ratio = std::numeric_limits<float>::infinity();
     if (e->n > 0) {
-        if (!kept_usable(e)) {
-            rc = evaluate_kept(e);
+        if (!hermite_kept_usable(e)) {
+            rc = hermite_evaluate_kept(e);
             if (rc != NBX_OK) return rc;
         }
         rc = grow(&e->d_hdt, &e->hdt_cap, nbx::hermite_dtmin_workspace(e->n));

@@ -220,6 +220,23 @@ struct nbx_engine {
                                           // nbx_acc_jerk, taken back by everything else that can change positions, velocities or
                                           // masses (positions_moved(), after_host_state_change) or the sweep's dimension
     int hermite_dim = 0;                  // ... and the DIM the sweep that produced them ran with
+    // K9, Hermite block time steps (engine_hermite_block.cpp): per-body (time in ticks, level) beside the kept pair, and workspaces
+    nbx::HermiteBody* d_hbt = nullptr;
+    size_t hbt_cap = 0;
+    int* d_hblist = nullptr;              // the block: indices of the due bodies, ascending (or nbx_acc_jerk_subset's list)
+    size_t hblist_cap = 0;
+    int* d_hbws = nullptr;                // the scheduler's head (t_next, n_active), then the workgroups' minima and counts
+    size_t hbws_cap = 0;
+    nbx::HermiteAJ* d_hbout = nullptr;    // nbx_acc_jerk_subset: (a, j) per list slot
+    size_t hbout_cap = 0;
+    nbx::HermiteHead* h_hbhead = nullptr; // pinned: where the 8-byte read of a block step lands
+    bool hblock_valid = false;            // d_hbt holds levels the next macro-step may start from.  Means something only while
+                                          // hermite_valid does: whatever re-evaluates a kept pair that was not usable drops it
+                                          // (evaluate_kept), and so does a shared nbx_step_hermite
+    bool hblock_any_dt = false;           // the levels were prescribed (nbx_hermite_block_set_levels): they serve the next dt_max
+    float hblock_dt_max = 0.0f;           // ... otherwise the dt_max they were made for
+    int hblock_steps = 0;                 // NBX_STAT_HERMITE_BLOCK_STEPS / _EVALS: block steps of the last macro-step, sum of n_active
+    long long hblock_evals = 0;
 
     // options
     int force_mode = 0, jsplit = 0, bpt = 0, dim_opt = 0, profile = 0, variant = -1, strict_kernel = 0;
@@ -460,6 +477,16 @@ int conserved_f64(nbx_engine* e, int count, double* out);
 int step_hermite(nbx_engine* e, float dt);
 int acc_jerk(nbx_engine* e, int cap, float* ax, float* ay, float* az, float* jx, float* jy, float* jz);
 int hermite_timestep(nbx_engine* e, float eta, float* dt_out);
+int hermite_ready(nbx_engine* e);      // a device, a configuration the sweep serves, the state uploaded
+int hermite_sweep_dim(const nbx_engine* e);
+bool hermite_kept_usable(const nbx_engine* e);
+int hermite_evaluate_kept(nbx_engine* e);   // (a0, j0) of the current state into e->d_hkept
+// engine_hermite_block.cpp: block time steps for the Hermite scheme (K9)
+int step_hermite_block(nbx_engine* e, float dt_max, float eta);
+int hermite_block_set_levels(nbx_engine* e, const int32_t* levels, int n);
+int hermite_block_levels(nbx_engine* e, int cap, int32_t* out);
+int hermite_kept(nbx_engine* e, int cap, float* ax, float* ay, float* az, float* jx, float* jy, float* jz);
+int acc_jerk_subset(nbx_engine* e, const int32_t* idx, int count, float* ax, float* ay, float* az, float* jx, float* jy, float* jz);
 int resolve_pending(nbx_engine* e);   // the verdicts of the speculatively enqueued Barnes-Hut steps, oldest first (no-op when none)
 void free_device(nbx_engine* e);
 uint64_t entropy_seed();

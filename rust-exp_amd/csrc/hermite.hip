@@ -34,7 +34,7 @@
 //   k_hermite_dtmin    min_i |a_i| / |j_i| over the kept (a0, j0): a fixed-order LDS tree per workgroup, then ONE workgroup over
 //                      the partials (the pattern of k_conserved64).  Bodies with |j_i| = 0 are skipped; none left: +inf.
 // Deterministic: no atomics, every order fixed by the launch shape (n, S, T).
-#include "kernels.h"
+#include "hermite_math.h"
 
 namespace nbx {
 
@@ -164,17 +164,7 @@ __device__ __forceinline__ HermiteAJ sum_partials(const HermiteAJ* __restrict__ 
     return r;
 }
 
-// the corrector, h = dt / 2 (exact), c12 = dt^2 / 12 (rounded once, on the host); every product and sum rounded on its own:
-//   v1 = (v + (a0 + a1) h) + (j0 - j1) c12        x1 = (x + (v + v1) h) + (a0 - a1) c12
-__device__ __forceinline__ float correct_v(float v, float a0, float a1, float j0, float j1, float h, float c12)
-{
-    return __fadd_rn(__fadd_rn(v, __fmul_rn(__fadd_rn(a0, a1), h)), __fmul_rn(__fsub_rn(j0, j1), c12));
-}
-__device__ __forceinline__ float correct_x(float x, float v, float v1, float a0, float a1, float h, float c12)
-{
-    return __fadd_rn(__fadd_rn(x, __fmul_rn(__fadd_rn(v, v1), h)), __fmul_rn(__fsub_rn(a0, a1), c12));
-}
-
+// (the corrector correct_v / correct_x and the ratio |a| / |j|: hermite_math.h, shared with the block step)
 __global__ __launch_bounds__(kTile) void k_hermite_correct(float4* __restrict__ posm, const int lo, const int n_targets,
                                                            float4* __restrict__ vel, const HermiteAJ* __restrict__ partial,
                                                            const int jsplit, const int stride, HermiteAJ* __restrict__ kept,
@@ -217,7 +207,6 @@ __device__ __forceinline__ float tree_min(float* red, const int tid, float r)
     return red[0];
 }
 
-// |a| / |j| = sqrt(|a|^2 / |j|^2): two sums of three squares, one IEEE division, one IEEE square root
 __global__ __launch_bounds__(kTile) void k_hermite_dtmin(const HermiteAJ* __restrict__ kept, const int n_targets,
                                                          float* __restrict__ block_min)
 {
@@ -225,12 +214,7 @@ __global__ __launch_bounds__(kTile) void k_hermite_dtmin(const HermiteAJ* __rest
     const int tid = threadIdx.x;
     const int i = blockIdx.x * kTile + tid;
     float r = __builtin_inff();
-    if (i < n_targets) {
-        const HermiteAJ k = kept[i];
-        const float a2 = __builtin_fmaf(k.a.z, k.a.z, __builtin_fmaf(k.a.y, k.a.y, __fmul_rn(k.a.x, k.a.x)));
-        const float j2 = __builtin_fmaf(k.j.z, k.j.z, __builtin_fmaf(k.j.y, k.j.y, __fmul_rn(k.j.x, k.j.x)));
-        if (j2 > 0.f) r = __fsqrt_rn(__fdiv_rn(a2, j2));
-    }
+    if (i < n_targets) r = hermite_ratio(kept[i]);
     r = tree_min(red, tid, r);
     if (tid == 0) block_min[blockIdx.x] = r;
 }

@@ -215,6 +215,46 @@ hipError_t launch_hermite_keep(int n_targets, const HermiteAJ* partial, int jspl
 size_t hermite_dtmin_workspace(int n_targets);
 hipError_t launch_hermite_dtmin(const HermiteAJ* kept, int n_targets, float* workspace, hipStream_t stream);
 
+// ---- K9 (hermite_block.hip): Hermite block time steps behind nbx_step_hermite_block / nbx_acc_jerk_subset ----
+// Time is integer: a macro-step of dt_max is kHermiteTicks ticks, a body at level l steps kHermiteTicks >> l of them.
+constexpr int kHermiteMaxLevel = 20;
+constexpr int kHermiteTicks = 1 << kHermiteMaxLevel;
+struct HermiteBody {   // per body, beside its kept (a0, j0): the time it stands at and its level
+    int t, level;
+};
+struct HermiteHead {   // what the scheduler tells the host once per block step: ONE 8-byte read
+    int t_next, n_active;
+};
+// per level: dt = dt_max 2^-l and the constants of predictor and corrector, computed in double and rounded once on the host --
+// those of launch_hermite_predict / launch_hermite_correct at dt.  tick = dt_max 2^-20.  eta <= 0: levels are frozen
+struct HermiteLevels {
+    float dt[kHermiteMaxLevel + 1], c2[kHermiteMaxLevel + 1], c3[kHermiteMaxLevel + 1], h[kHermiteMaxLevel + 1], c12[kHermiteMaxLevel + 1];
+    float tick, eta;
+};
+HermiteLevels hermite_levels(float dt_max, float eta);
+int hermite_block_targets(int n_active, int n);   // T, targets per lane, of a block of n_active bodies out of n (n_active == n: K8's)
+int hermite_block_stride(int n_active, int t);    // list slots per partial slab: the block rounded up to whole workgroups
+// the source split of a block: grows until the block's workgroups fill the CUs, every wave keeping a whole tile of sources;
+// n_active == n: exactly hermite_split(n, ...)
+int hermite_block_split(int n_active, int n, int tiles_total, int cu_count, int t);
+size_t hermite_block_workspace(int n);   // ints: the head, then the workgroups' minima and counts
+// bt[i] = (0, the level eta |a_i| / |j_i| asks for; eta <= 0: level 0) from the kept pairs
+hipError_t launch_block_init_levels(const HermiteAJ* kept, int n, const HermiteLevels& lv, HermiteBody* bt, hipStream_t stream);
+// head = (min_i t_i + step_i, number of bodies due then); list[0 .. n_active) = their indices, ascending.  No atomics
+hipError_t launch_block_schedule(const HermiteBody* bt, int n, int* workspace, int* list, hipStream_t stream);
+// src[i] = body i advanced from its own time t_i to t_next along its kept pair; zero records for n <= i < n_pad
+hipError_t launch_block_predict(const float4* posm, const float4* vel, const HermiteAJ* kept, const HermiteBody* bt, int n, int n_pad,
+                                int t_next, const HermiteLevels& lv, HermiteSrc* src, hipStream_t stream);
+// partial[s][slot] = (a, j) of target src[list[slot]] over the s-th of `jsplit` source ranges, in K8's summation order.
+// info->variant = 41, bpt = t (1 or 2)
+hipError_t launch_block_sweep(const HermiteSrc* src, const int* list, int n_active, int tiles_total, int jsplit, int dim, int t,
+                              HermiteAJ* partial, hipStream_t stream, ForceLaunch* info);
+// the corrector on the listed bodies (scattered to posm, vel, kept), t_i = t_next (0 at the end of the macro-step), new level
+hipError_t launch_block_correct(float4* posm, float4* vel, HermiteAJ* kept, HermiteBody* bt, const int* list, int n_active,
+                                const HermiteAJ* partial, int jsplit, int stride, int t_next, const HermiteLevels& lv, hipStream_t stream);
+// out[slot] = the partials of the slot in ascending order; nothing else is written
+hipError_t launch_block_keep(int n_active, const HermiteAJ* partial, int jsplit, int stride, HermiteAJ* out, hipStream_t stream);
+
 // strict (bit-exact) pair: ascending j per target, IEEE divide, no contraction. 2-D.
 // kernel: 16 or 8 = workgroups of that many waves per 64 targets (term producers + one summing wave), 1 = one thread per body,
 // anything else = by size (strict_kernel_choice); info->variant = -(kernel). Results are bit-identical whichever runs.

@@ -50,6 +50,9 @@ NBX_STAT_BH_CLASS_SWITCHES = 4
 NBX_STAT_BH_COLD_RESORTS = 5
 NBX_STAT_BH_CHAIN_MERGED = 6
 NBX_STAT_BH_CHAIN_APPROX = 7
+NBX_STAT_HERMITE_BLOCK_STEPS = 8
+NBX_STAT_HERMITE_BLOCK_EVALS = 9
+NBX_HERMITE_MAX_LEVEL = 20
 
 NBX_GROUP_INFO_EXCHANGE = 0
 NBX_GROUP_INFO_RCCL_RANKS = 1
@@ -223,6 +226,16 @@ def lib():
     L.nbx_acc_jerk.restype = i32
     L.nbx_hermite_timestep.argtypes = [E, C.c_float, C.POINTER(C.c_float)]
     L.nbx_hermite_timestep.restype = i32
+    L.nbx_step_hermite_block.argtypes = [E, C.c_float, C.c_float]
+    L.nbx_step_hermite_block.restype = i32
+    L.nbx_hermite_block_set_levels.argtypes = [E, C.c_void_p, i32]
+    L.nbx_hermite_block_set_levels.restype = i32
+    L.nbx_hermite_block_levels.argtypes = [E, i32, C.c_void_p]
+    L.nbx_hermite_block_levels.restype = i32
+    L.nbx_hermite_kept.argtypes = [E, i32] + [C.c_void_p] * 6
+    L.nbx_hermite_kept.restype = i32
+    L.nbx_acc_jerk_subset.argtypes = [E, C.c_void_p, i32] + [C.c_void_p] * 6
+    L.nbx_acc_jerk_subset.restype = i32
     L.nbx_draw.argtypes = [E, i32, i32, C.c_void_p]
     L.nbx_draw.restype = i32
     L.nbx_bh_tree_dump.argtypes = [E, C.c_void_p, i32]
@@ -536,6 +549,36 @@ class NBodyEngine:
         dt = C.c_float()
         _check(self._L.nbx_hermite_timestep(self._h, eta, C.byref(dt)))
         return float(dt.value)
+
+    def step_hermite_block(self, dt_max, eta):
+        """Every body forward by dt_max through Hermite block steps (nbx_step_hermite_block): each body on its own step
+        dt_max 2^-level, chosen from eta |a| / |j|; eta <= 0 keeps the levels as they are."""
+        _check(self._L.nbx_step_hermite_block(self._h, dt_max, eta))
+
+    def set_hermite_block_levels(self, levels):
+        """Prescribes every body's level, 0 .. NBX_HERMITE_MAX_LEVEL (nbx_hermite_block_set_levels)."""
+        lv = np.ascontiguousarray(levels, dtype=np.int32)
+        _check(self._L.nbx_hermite_block_set_levels(self._h, _p(lv), len(lv)))
+
+    def hermite_block_levels(self):
+        """The bodies' levels as an int32 array (nbx_hermite_block_levels)."""
+        out = np.zeros(self.num_particles(), np.int32)
+        _check(self._L.nbx_hermite_block_levels(self._h, len(out), _p(out)))
+        return out
+
+    def hermite_kept(self):
+        """The kept (a0, j0) as six float32 arrays, without a new evaluation (nbx_hermite_kept)."""
+        n = self.num_particles()
+        out = [np.zeros(n, np.float32) for _ in range(6)]
+        _check(self._L.nbx_hermite_kept(self._h, n, *[_p(a) for a in out]))
+        return tuple(out)
+
+    def acc_jerk_subset(self, idx):
+        """ax, ay, az, jx, jy, jz of the listed bodies at the current state (nbx_acc_jerk_subset); state and kept pair untouched."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        out = [np.zeros(len(idx), np.float32) for _ in range(6)]
+        _check(self._L.nbx_acc_jerk_subset(self._h, _p(idx), len(idx), *[_p(a) for a in out]))
+        return tuple(out)
 
     def set_bh_tree(self, where):
         """'host' (reference-faithful insertion build), 'device' (bh_build.hip) or 'auto' (default: device in the fast
