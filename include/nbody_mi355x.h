@@ -177,6 +177,15 @@ enum nbx_option {
                                     * an nbx_group and NBX_OPT_SOURCE_PRECISION = 16 return NBX_ERR_STATE.  A root box so large that
                                     * two bodies further apart than EPS share a level-21 cell: NBX_ERR_TREE_DEPTH, state untouched.
                                     * There is no "auto": the default never changes behaviour */
+    NBX_OPT_HERMITE_BLOCK_TRAIN = 23, /* nbx_step_hermite_block: 0 (default) = every block step is the scheduler's four kernels, one
+                                    * synchronous 8-byte read, predict, sweep, correct.  L = 1 .. 256: block steps of at most 64 due
+                                    * bodies ("small") are served by two kernels each (hermite_train.hip: a sweep that splits the sources
+                                    * across lanes and predicts them in registers, then ONE workgroup that corrects the block and
+                                    * schedules the next one), and the host enqueues L of them per read; a larger block, the all-active
+                                    * one included, runs the default kernels unchanged, so a macro-step without a small block is
+                                    * bit-identical to 0.  Small blocks sum their pairs in another (fixed) order than the default
+                                    * path: same bound, other bits; deterministic.  With L > 0 nbx_acc_jerk_subset uses the same
+                                    * sweep for count <= 64 (nbx_last_launch: variant 42).  Anything else: NBX_ERR_INVALID */
     NBX_OPT_SOURCE_PRECISION = 6   /* 32 (default) or 16: all-pairs SOURCES read from a half4 (x,y,z,m) copy, 8 B/body;
                                     * targets, accumulators and the integrated state stay fp32 (fast mode only) */
 };
@@ -220,7 +229,10 @@ enum nbx_stat {
                                     * At most max(16, n/2000) in a build that was accepted: beyond that the step goes to the host build
                                     * (NBX_STAT_BH_REFUSAL 0x20000) */
     NBX_STAT_HERMITE_BLOCK_STEPS = 8, /* block steps of the last nbx_step_hermite_block macro-step */
-    NBX_STAT_HERMITE_BLOCK_EVALS = 9  /* ... and the sum of their block sizes: body evaluations (n per shared step) */
+    NBX_STAT_HERMITE_BLOCK_EVALS = 9, /* ... and the sum of their block sizes: body evaluations (n per shared step) */
+    NBX_STAT_HERMITE_BLOCK_TRAIN_STEPS = 10, /* ... those of its block steps that the train kernels served (NBX_OPT_HERMITE_BLOCK_TRAIN; 0 when off) */
+    NBX_STAT_HERMITE_BLOCK_READS = 11 /* ... and the synchronous reads of the scheduler's head it took: one per block step when the
+                                    * train is off, one per train of small blocks plus one per large block when on */
 };
 
 enum nbx_kernel_id {

@@ -138,6 +138,10 @@ int32_t nbx_set_option(nbx_engine* e, int32_t option, int64_t value)
             if (value != 2 && value != 3) return fail(NBX_ERR_INVALID, "bh dim must be 2 (quadtree on x, y) or 3 (octree)");
             e->bh_dim = (int)value;
             return NBX_OK;
+        case NBX_OPT_HERMITE_BLOCK_TRAIN:
+            if (value < 0 || value > 256) return fail(NBX_ERR_INVALID, "hermite block train must be 0 (off) or 1 .. 256 block steps per host read");
+            e->hblock_train = (int)value;
+            return NBX_OK;
         case NBX_OPT_BH_FOLD:
             if (value != 0 && value != 1 && value != -1) return fail(NBX_ERR_INVALID, "bh fold must be 0 (exact sums), 1 (reference fold) or -1 (by size)");
             e->bh_fold = (int)value;
@@ -176,6 +180,7 @@ int64_t nbx_get_option(const nbx_engine* e, int32_t option)
         case NBX_OPT_BH_WALK: return e->bh_walk;
         case NBX_OPT_BH_FUSE_KICK: return e->bh_fuse_kick;
         case NBX_OPT_BH_DIM: return e->bh_dim;
+        case NBX_OPT_HERMITE_BLOCK_TRAIN: return e->hblock_train;
         default: return NBX_ERR_INVALID;
     }
 }
@@ -202,6 +207,8 @@ int64_t nbx_get_stat(const nbx_engine* e, int32_t stat)
         case NBX_STAT_DRAW_AMBIGUOUS: return e->draw_ambiguous;
         case NBX_STAT_HERMITE_BLOCK_STEPS: return e->hblock_steps;
         case NBX_STAT_HERMITE_BLOCK_EVALS: return e->hblock_evals;
+        case NBX_STAT_HERMITE_BLOCK_TRAIN_STEPS: return e->hblock_train_steps;
+        case NBX_STAT_HERMITE_BLOCK_READS: return e->hblock_reads;
         default: return INT64_MIN;
     }
 }
@@ -215,7 +222,7 @@ int32_t nbx_query_option(const nbx_engine* e, int32_t option, int64_t* value)
         case NBX_OPT_FORCE_MODE: case NBX_OPT_JSPLIT: case NBX_OPT_BODIES_PER_THREAD: case NBX_OPT_DIM: case NBX_OPT_PROFILE:
         case NBX_OPT_KERNEL_VARIANT: case NBX_OPT_SOURCE_PRECISION: case NBX_OPT_DRAW_DEVICE: case NBX_OPT_BH_TREE: case NBX_OPT_BH_WAVE:
         case NBX_OPT_STRICT_KERNEL: case NBX_OPT_BH_FOLD: case NBX_OPT_BH_ASYNC: case NBX_OPT_BH_WALK: case NBX_OPT_BH_FUSE_KICK:
-        case NBX_OPT_BH_DIM:
+        case NBX_OPT_BH_DIM: case NBX_OPT_HERMITE_BLOCK_TRAIN:
             if (value) *value = nbx_get_option(e, option);
             return NBX_OK;
         default:

@@ -407,6 +407,8 @@ void free_device(nbx_engine* e)
     if (e->d_hbws) (void)hipFree(e->d_hbws);
     if (e->d_hbout) (void)hipFree(e->d_hbout);
     if (e->h_hbhead) (void)hipHostFree(e->h_hbhead);
+    if (e->d_htrain) (void)hipFree(e->d_htrain);
+    if (e->h_htrain) (void)hipHostFree(e->h_htrain);
     if (e->d_exc_rec) (void)hipFree(e->d_exc_rec);
     if (e->d_tree_ws) (void)hipFree(e->d_tree_ws);
     if (e->d_slab_ws) (void)hipFree(e->d_slab_ws);

@@ -7,6 +7,8 @@
 // steps divide the macro-step, so its last block holds every body and leaves them at one time with posm / vel consistent; nothing
 // is read after it.  The block state -- (time, level) per body in e->d_hbt -- lives and dies with the kept (a0, j0) of K8
 // (nbx_engine::hermite_valid), plus its own flag for what a shared nbx_step_hermite or another dt_max takes away.
+// NBX_OPT_HERMITE_BLOCK_TRAIN = L > 0 hands blocks of at most 64 bodies to K10 (hermite_train.hip), L block steps per read:
+// train_macro_step below.
 #include <cmath>
 
 #include "engine_internal.h"
@@ -54,6 +56,94 @@ static int block_buffers(nbx_engine* e)
     return NBX_OK;
 }
 
+// one block step of K9 on the list in e->d_hblist: predict every body to t_next, sweep, correct the n_active listed bodies
+static int block_step(nbx_engine* e, const nbx::HermiteLevels& lv, int t_next, int n_active)
+{
+    int stride = 0;
+    {
+        ProfScope ps(e, NBX_K_INTEGRATE);
+        HIP_TRY(nbx::launch_block_predict(e->d_posm, e->d_vel, e->d_hkept, e->d_hbt, e->n, e->n_pad, t_next, lv, e->d_hsrc, e->stream));
+    }
+    const int rc = block_sweep(e, n_active, &stride);
+    if (rc != NBX_OK) return rc;
+    {
+        ProfScope ps(e, NBX_K_INTEGRATE);
+        HIP_TRY(nbx::launch_block_correct(e->d_posm, e->d_vel, e->d_hkept, e->d_hbt, e->d_hblist, n_active, e->d_hpart, e->last.jsplit,
+                                          stride, t_next, lv, e->stream));
+    }
+    e->hblock_steps++;
+    e->hblock_evals += n_active;
+    return NBX_OK;
+}
+
+// G of K10's sweep and room for its partials
+static int train_groups(nbx_engine* e, int* groups)
+{
+    *groups = nbx::hermite_train_groups(e->n_pad / kTile, e->cu_count, e->jsplit);
+    return grow(&e->d_hpart, &e->hpart_cap, (size_t)*groups * (size_t)nbx::kTrainMaxBlock);
+}
+
+// A macro-step with NBX_OPT_HERMITE_BLOCK_TRAIN = L > 0 (hermite_train.hip).  The scheduler once; then trains of L cars -- a car is
+// a block step of at most kTrainMaxBlock bodies, sweep + finish, that finds its block in device memory and leaves the next one
+// there -- with ONE read of head + train record behind each train.  A car that meets a larger block (or the end of the macro-step)
+// does nothing, and so do the cars behind it: the host then runs K9's block step on the list that is already there, schedules
+// again and goes on with trains.
+static int train_macro_step(nbx_engine* e, const nbx::HermiteLevels& lv)
+{
+    const int n = e->n, dim = hermite_sweep_dim(e);
+    int groups = 0;
+    int rc = train_groups(e, &groups);
+    if (rc != NBX_OK) return rc;
+    rc = grow(&e->d_htrain, &e->htrain_cap, 1);
+    if (rc != NBX_OK) return rc;
+    if (!e->h_htrain) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->h_htrain), sizeof(*e->h_htrain)));
+    nbx::HermiteHead* d_head = reinterpret_cast<nbx::HermiteHead*>(e->d_hbws);
+    int large_steps = 0;          // block steps K9 served
+    long long large_evals = 0;
+    bool schedule = true;
+    for (int t_done = 0; t_done < nbx::kHermiteTicks;) {
+        if (schedule) {
+            ProfScope ps(e, NBX_K_INTEGRATE);
+            HIP_TRY(nbx::launch_block_schedule(e->d_hbt, n, e->d_hbws, e->d_hblist, e->stream));
+            if (t_done == 0) HIP_TRY(nbx::launch_train_reset(e->d_htrain, e->stream));
+            schedule = false;
+        }
+        for (int car = 0; car < e->hblock_train; car++) {
+            {
+                ProfScope ps(e, NBX_K_FORCE);
+                HIP_TRY(nbx::launch_train_sweep(e->d_posm, e->d_vel, e->d_hkept, e->d_hbt, n, e->n_pad / kTile, groups, dim, d_head, e->d_htrain,
+                                                e->d_hblist, 0, lv, e->d_hpart, e->stream, &e->last));
+            }
+            ProfScope ps(e, NBX_K_INTEGRATE);
+            HIP_TRY(nbx::launch_train_finish(e->d_posm, e->d_vel, e->d_hkept, e->d_hbt, n, e->d_hblist, d_head, e->d_htrain, e->d_hpart, groups,
+                                             lv, e->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(&e->h_htrain->head, d_head, sizeof(nbx::HermiteHead), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(&e->h_htrain->train, e->d_htrain, sizeof(nbx::HermiteTrain), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(wait_stream(e->stream, n <= kSpinMaxBodies));
+        e->hblock_reads++;
+        const nbx::HermiteTrain tr = e->h_htrain->train;
+        if (tr.steps < e->hblock_train_steps || tr.steps > e->hblock_train_steps + e->hblock_train)
+            return fail(NBX_ERR_STATE, "the block train reports %d steps after %d in a train of %d", tr.steps, e->hblock_train_steps, e->hblock_train);
+        if (tr.steps > e->hblock_train_steps) t_done = tr.t_done;
+        e->hblock_train_steps = tr.steps;
+        e->hblock_steps = large_steps + tr.steps;
+        e->hblock_evals = large_evals + tr.evals;
+        if (tr.finished || t_done >= nbx::kHermiteTicks) break;
+        const int t_next = e->h_htrain->head.t_next, n_active = e->h_htrain->head.n_active;
+        if (t_next <= t_done || t_next > nbx::kHermiteTicks || n_active < 1 || n_active > n)
+            return fail(NBX_ERR_STATE, "the block scheduler returned t_next = %d after %d with %d of %d bodies", t_next, t_done, n_active, n);
+        if (n_active <= nbx::kTrainMaxBlock) continue;   // the train ran out of cars: the next one
+        rc = block_step(e, lv, t_next, n_active);
+        if (rc != NBX_OK) return rc;
+        large_steps++;
+        large_evals += n_active;
+        t_done = t_next;
+        schedule = true;
+    }
+    return NBX_OK;
+}
+
 static bool block_usable(const nbx_engine* e) { return hermite_kept_usable(e) && e->hblock_valid && e->d_hbt; }
 
 int step_hermite_block(nbx_engine* e, float dt_max, float eta)
@@ -63,6 +153,8 @@ int step_hermite_block(nbx_engine* e, float dt_max, float eta)
     if (!(dt_max > 0.0f) || !std::isfinite(dt_max)) return fail(NBX_ERR_INVALID, "dt_max must be positive and finite");
     e->hblock_steps = 0;
     e->hblock_evals = 0;
+    e->hblock_train_steps = 0;
+    e->hblock_reads = 0;
     const int n = e->n;
     if (n == 0) return NBX_OK;
     if (!hermite_kept_usable(e)) {
@@ -79,31 +171,25 @@ int step_hermite_block(nbx_engine* e, float dt_max, float eta)
     e->hermite_valid = false;   // until the last corrector is enqueued
     e->hblock_valid = false;
     const int dim = hermite_sweep_dim(e);
-    for (int t_done = 0; t_done < nbx::kHermiteTicks;) {
-        {
-            ProfScope ps(e, NBX_K_INTEGRATE);
-            HIP_TRY(nbx::launch_block_schedule(e->d_hbt, n, e->d_hbws, e->d_hblist, e->stream));
-        }
-        HIP_TRY(hipMemcpyAsync(e->h_hbhead, e->d_hbws, sizeof(nbx::HermiteHead), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(wait_stream(e->stream, n <= kSpinMaxBodies));
-        const int t_next = e->h_hbhead->t_next, n_active = e->h_hbhead->n_active;
-        if (t_next <= t_done || t_next > nbx::kHermiteTicks || n_active < 1 || n_active > n)
-            return fail(NBX_ERR_STATE, "the block scheduler returned t_next = %d after %d with %d of %d bodies", t_next, t_done, n_active, n);
-        int stride = 0;
-        {
-            ProfScope ps(e, NBX_K_INTEGRATE);
-            HIP_TRY(nbx::launch_block_predict(e->d_posm, e->d_vel, e->d_hkept, e->d_hbt, n, e->n_pad, t_next, lv, e->d_hsrc, e->stream));
-        }
-        rc = block_sweep(e, n_active, &stride);
+    if (e->hblock_train > 0) {
+        rc = train_macro_step(e, lv);
         if (rc != NBX_OK) return rc;
-        {
-            ProfScope ps(e, NBX_K_INTEGRATE);
-            HIP_TRY(nbx::launch_block_correct(e->d_posm, e->d_vel, e->d_hkept, e->d_hbt, e->d_hblist, n_active, e->d_hpart, e->last.jsplit,
-                                              stride, t_next, lv, e->stream));
+    } else {
+        for (int t_done = 0; t_done < nbx::kHermiteTicks;) {
+            {
+                ProfScope ps(e, NBX_K_INTEGRATE);
+                HIP_TRY(nbx::launch_block_schedule(e->d_hbt, n, e->d_hbws, e->d_hblist, e->stream));
+            }
+            HIP_TRY(hipMemcpyAsync(e->h_hbhead, e->d_hbws, sizeof(nbx::HermiteHead), hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(wait_stream(e->stream, n <= kSpinMaxBodies));
+            e->hblock_reads++;
+            const int t_next = e->h_hbhead->t_next, n_active = e->h_hbhead->n_active;
+            if (t_next <= t_done || t_next > nbx::kHermiteTicks || n_active < 1 || n_active > n)
+                return fail(NBX_ERR_STATE, "the block scheduler returned t_next = %d after %d with %d of %d bodies", t_next, t_done, n_active, n);
+            rc = block_step(e, lv, t_next, n_active);
+            if (rc != NBX_OK) return rc;
+            t_done = t_next;
         }
-        e->hblock_steps++;
-        e->hblock_evals += n_active;
-        t_done = t_next;
     }
     e->positions_moved();       // (the order-sorted copy of the positions is stale from here) ...
     e->hermite_valid = true;    // ... but kept pair and levels are the ones this macro-step left
@@ -201,6 +287,18 @@ int acc_jerk_subset(nbx_engine* e, const int32_t* idx, int count, float* ax, flo
     rc = grow(&e->d_hbout, &e->hbout_cap, (size_t)count);
     if (rc != NBX_OK) return rc;
     HIP_TRY(hipMemcpyAsync(e->d_hblist, idx, sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, e->stream));
+    if (e->hblock_train > 0 && count <= nbx::kTrainMaxBlock) {   // K10's sweep reads posm / vel itself: no source records
+        int groups = 0;
+        rc = train_groups(e, &groups);
+        if (rc != NBX_OK) return rc;
+        {
+            ProfScope ps(e, NBX_K_FORCE);
+            HIP_TRY(nbx::launch_train_sweep(e->d_posm, e->d_vel, nullptr, nullptr, e->n, e->n_pad / kTile, groups, hermite_sweep_dim(e), nullptr,
+                                            nullptr, e->d_hblist, count, nbx::HermiteLevels{}, e->d_hpart, e->stream, &e->last));
+        }
+        HIP_TRY(nbx::launch_block_keep(count, e->d_hpart, groups, nbx::kTrainMaxBlock, e->d_hbout, e->stream));
+        return download_aj(e, e->d_hbout, count, ax, ay, az, jx, jy, jz);
+    }
     {   // the bodies as they are: the kept pair is neither read nor written
         ProfScope ps(e, NBX_K_INTEGRATE);
         HIP_TRY(nbx::launch_hermite_predict(e->d_posm, e->d_vel, nullptr, e->n, e->n_pad, false, 0.0f, e->d_hsrc, e->stream));

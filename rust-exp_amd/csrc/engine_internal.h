@@ -237,6 +237,14 @@ struct nbx_engine {
     float hblock_dt_max = 0.0f;           // ... otherwise the dt_max they were made for
     int hblock_steps = 0;                 // NBX_STAT_HERMITE_BLOCK_STEPS / _EVALS: block steps of the last macro-step, sum of n_active
     long long hblock_evals = 0;
+    // K10, small blocks in trains (hermite_train.hip)
+    int hblock_train = 0;                 // NBX_OPT_HERMITE_BLOCK_TRAIN: 0 = off (default), 1 .. 256 = block steps enqueued per host read
+    nbx::HermiteTrain* d_htrain = nullptr;   // the train's record, a buffer of its own
+    size_t htrain_cap = 0;
+    struct HermiteTrainRead { nbx::HermiteHead head; nbx::HermiteTrain train; };
+    HermiteTrainRead* h_htrain = nullptr; // pinned: where head + record land, once per train
+    int hblock_train_steps = 0;           // NBX_STAT_HERMITE_BLOCK_TRAIN_STEPS: block steps of the last macro-step the train kernels served
+    int hblock_reads = 0;                 // NBX_STAT_HERMITE_BLOCK_READS: synchronous head reads of the last macro-step
 
     // options
     int force_mode = 0, jsplit = 0, bpt = 0, dim_opt = 0, profile = 0, variant = -1, strict_kernel = 0;

@@ -32,12 +32,13 @@
 //                              fp32: it is deliberately not used
 //   k_block_init_levels        level = the first with dt(level) <= eta |a| / |j| of the kept pair, clamped to 0 .. 20; t_i = 0
 //   k_block_keep               the partials of a slot in ascending order, (a, j) only (nbx_acc_jerk_subset)
+// The prediction of a body and the corrector with its level rule live in hermite_block_math.h: K10 (hermite_train.hip) performs them too.
 // All steps divide 2^20, so a macro-step ends with a block in which every body is due; that block's corrector leaves t_i = 0.
 // Deterministic: no atomics anywhere, every order fixed by (n, the levels, S).
 #include <algorithm>
 #include <cmath>
 
-#include "hermite_math.h"
+#include "hermite_block_math.h"
 
 namespace nbx {
 
@@ -47,8 +48,6 @@ namespace {
 // size tried, 1 .. 65 536 of 262 144 bodies -- by 20 % where one workgroup row is all there is, by 3 - 6 % above; larger partial
 // blocks were not measured and keep K8's T = 2, as the all-active block does by definition
 constexpr int kTwoTargetsFrom = 131072;
-
-__device__ __forceinline__ int step_of(const int level) { return kHermiteTicks >> level; }
 
 __device__ __forceinline__ int tree_min(int* red, const int tid, int r)
 {
@@ -141,26 +140,7 @@ __global__ __launch_bounds__(kTile) void k_block_predict(const float4* __restric
     if (i >= n_pad) return;
     HermiteSrc r{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (i < n) {
-        const float4 p = posm[i];
-        const float4 v = vel[i];
-        const HermiteAJ k = kept[i];
-        const HermiteBody b = bt[i];
-        const int span = t_next - b.t;
-        float dt, c2, c3;
-        if (span == step_of(b.level)) {
-            dt = lv.dt[b.level]; c2 = lv.c2[b.level]; c3 = lv.c3[b.level];
-        } else {
-            dt = __fmul_rn((float)span, lv.tick);
-            c2 = __fmul_rn(__fmul_rn(0.5f, dt), dt);
-            c3 = __fmul_rn(__fmul_rn(c2, dt), 1.0f / 3.0f);
-        }
-        r.m = p.w;
-        r.x = __fadd_rn(__fadd_rn(__fadd_rn(p.x, __fmul_rn(dt, v.x)), __fmul_rn(c2, k.a.x)), __fmul_rn(c3, k.j.x));
-        r.y = __fadd_rn(__fadd_rn(__fadd_rn(p.y, __fmul_rn(dt, v.y)), __fmul_rn(c2, k.a.y)), __fmul_rn(c3, k.j.y));
-        r.z = __fadd_rn(__fadd_rn(__fadd_rn(p.z, __fmul_rn(dt, v.z)), __fmul_rn(c2, k.a.z)), __fmul_rn(c3, k.j.z));
-        r.vx = __fadd_rn(__fadd_rn(v.x, __fmul_rn(dt, k.a.x)), __fmul_rn(c2, k.j.x));
-        r.vy = __fadd_rn(__fadd_rn(v.y, __fmul_rn(dt, k.a.y)), __fmul_rn(c2, k.j.y));
-        r.vz = __fadd_rn(__fadd_rn(v.z, __fmul_rn(dt, k.a.z)), __fmul_rn(c2, k.j.z));
+        r = block_predict_body(posm[i], vel[i], kept[i], bt[i], t_next, lv);   // (hermite_block_math.h: K10 predicts with it too)
     }
     src[i] = r;
 }
@@ -268,31 +248,7 @@ __global__ __launch_bounds__(kTile) void k_block_correct(float4* __restrict__ po
     const int slot = blockIdx.x * kTile + threadIdx.x;
     if (slot >= n_active) return;
     const int i = list[slot];
-    const HermiteAJ n1 = sum_partials(partial, jsplit, stride, slot);
-    const HermiteAJ n0 = kept[i];
-    int level = bt[i].level;
-    const float h = lv.h[level], c12 = lv.c12[level];
-    float4 v = vel[i];
-    float4 p = posm[i];
-    const float v1x = correct_v(v.x, n0.a.x, n1.a.x, n0.j.x, n1.j.x, h, c12);
-    const float v1y = correct_v(v.y, n0.a.y, n1.a.y, n0.j.y, n1.j.y, h, c12);
-    const float v1z = correct_v(v.z, n0.a.z, n1.a.z, n0.j.z, n1.j.z, h, c12);
-    p.x = correct_x(p.x, v.x, v1x, n0.a.x, n1.a.x, h, c12);
-    p.y = correct_x(p.y, v.y, v1y, n0.a.y, n1.a.y, h, c12);
-    p.z = correct_x(p.z, v.z, v1z, n0.a.z, n1.a.z, h, c12);
-    v.x = v1x; v.y = v1y; v.z = v1z;
-    posm[i] = p;
-    vel[i] = v;
-    kept[i] = n1;
-    if (lv.eta > 0.f) {
-        const float dt_req = __fmul_rn(lv.eta, hermite_ratio(n1));
-        if (lv.dt[level] > dt_req && level < kHermiteMaxLevel) {
-            do level++; while (lv.dt[level] > dt_req && level < kHermiteMaxLevel);
-        } else if (level > 0 && lv.dt[level - 1] <= dt_req && (t_next & (2 * step_of(level) - 1)) == 0) {
-            level--;
-        }
-    }
-    bt[i] = HermiteBody{t_next == kHermiteTicks ? 0 : t_next, level};
+    block_correct_body(posm, vel, kept, bt, i, sum_partials(partial, jsplit, stride, slot), t_next, lv);   // (hermite_block_math.h)
 }
 
 __global__ __launch_bounds__(kTile) void k_block_keep(const int n_active, const HermiteAJ* __restrict__ partial, const int jsplit,

@@ -255,6 +255,27 @@ hipError_t launch_block_correct(float4* posm, float4* vel, HermiteAJ* kept, Herm
 // out[slot] = the partials of the slot in ascending order; nothing else is written
 hipError_t launch_block_keep(int n_active, const HermiteAJ* partial, int jsplit, int stride, HermiteAJ* out, hipStream_t stream);
 
+// ---- K10 (hermite_train.hip): block steps of at most kTrainMaxBlock bodies, enqueued in trains (NBX_OPT_HERMITE_BLOCK_TRAIN) ----
+constexpr int kTrainMaxBlock = 64;   // a SMALL block: one wave of corrector threads, 2 KB of target records; also the partials' stride
+struct HermiteTrain {   // what the train's cars have done since launch_train_reset, beside the HermiteHead they keep current
+    int t_done, steps, finished, pad;   // the time reached, the block steps run, 1 once the block at 2^20 ticks is corrected
+    long long evals;                    // sum of the block sizes
+};
+// G, the workgroups of the sweep = its source split: jsplit if positive, else one per CU; at most one per source tile
+int hermite_train_groups(int tiles_total, int cu_count, int jsplit);
+hipError_t launch_train_reset(HermiteTrain* train, hipStream_t stream);
+// partial[g][slot] (stride kTrainMaxBlock) = (a, j) of body list[slot] over the g-th of `groups` source ranges; sources split across
+// lanes, predicted in registers.  head != nullptr: a car -- (t_next, n_active) from *head, bodies predicted from their own times; does
+// nothing if n_active > kTrainMaxBlock or train->finished.  head == nullptr: the bodies as they are, `count` <= kTrainMaxBlock
+// listed (kept, bt, train unused).  info->variant = 42, jsplit = groups, bpt = 1
+hipError_t launch_train_sweep(const float4* posm, const float4* vel, const HermiteAJ* kept, const HermiteBody* bt, int n, int tiles_total,
+                              int groups, int dim, const HermiteHead* head, const HermiteTrain* train, const int* list, int count,
+                              const HermiteLevels& lv, HermiteAJ* partial, hipStream_t stream, ForceLaunch* info);
+// the second half of a car, one workgroup: partials in ascending order, corrector and level rule on the listed bodies, then the NEXT
+// block's (t_next, n_active) into *head and its list into `list`; *train updated.  The same no-op rule
+hipError_t launch_train_finish(float4* posm, float4* vel, HermiteAJ* kept, HermiteBody* bt, int n, int* list, HermiteHead* head,
+                               HermiteTrain* train, const HermiteAJ* partial, int groups, const HermiteLevels& lv, hipStream_t stream);
+
 // strict (bit-exact) pair: ascending j per target, IEEE divide, no contraction. 2-D.
 // kernel: 16 or 8 = workgroups of that many waves per 64 targets (term producers + one summing wave), 1 = one thread per body,
 // anything else = by size (strict_kernel_choice); info->variant = -(kernel). Results are bit-identical whichever runs.

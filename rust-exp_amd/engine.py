@@ -40,6 +40,7 @@ NBX_OPT_BH_ASYNC = 15
 NBX_OPT_BH_WALK = 18
 NBX_OPT_BH_FUSE_KICK = 20
 NBX_OPT_BH_DIM = 22              # (21 is not an option)
+NBX_OPT_HERMITE_BLOCK_TRAIN = 23
 # (10-12 and 17 became enum nbx_stat in round 5; 16 and 19 -- measured losers -- were removed)
 
 NBX_STAT_BH_FALLBACKS = 0
@@ -52,6 +53,8 @@ NBX_STAT_BH_CHAIN_MERGED = 6
 NBX_STAT_BH_CHAIN_APPROX = 7
 NBX_STAT_HERMITE_BLOCK_STEPS = 8
 NBX_STAT_HERMITE_BLOCK_EVALS = 9
+NBX_STAT_HERMITE_BLOCK_TRAIN_STEPS = 10
+NBX_STAT_HERMITE_BLOCK_READS = 11
 NBX_HERMITE_MAX_LEVEL = 20
 
 NBX_GROUP_INFO_EXCHANGE = 0
@@ -554,6 +557,11 @@ class NBodyEngine:
         """Every body forward by dt_max through Hermite block steps (nbx_step_hermite_block): each body on its own step
         dt_max 2^-level, chosen from eta |a| / |j|; eta <= 0 keeps the levels as they are."""
         _check(self._L.nbx_step_hermite_block(self._h, dt_max, eta))
+
+    def set_hermite_block_train(self, length):
+        """Block steps enqueued per host read, 1 .. 256; 0 (default) = off (NBX_OPT_HERMITE_BLOCK_TRAIN).  On: blocks of at most 64
+        due bodies run the small-block kernels, and so does acc_jerk_subset with up to 64 indices."""
+        self.set_option(NBX_OPT_HERMITE_BLOCK_TRAIN, length)
 
     def set_hermite_block_levels(self, levels):
         """Prescribes every body's level, 0 .. NBX_HERMITE_MAX_LEVEL (nbx_hermite_block_set_levels)."""
