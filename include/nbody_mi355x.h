@@ -93,7 +93,7 @@ enum nbx_status {
     NBX_ERR_STATE = -7       /* call not valid in the engine's current configuration */
 };
 
-/* 15 options (numbers are stable; 10-12 and 17 moved to nbx_stat, 16 and 19 -- measured losers -- were removed in round 5) */
+/* 16 options (numbers are stable; 10-12 and 17 moved to nbx_stat, 16 and 19 -- measured losers -- were removed in round 5) */
 enum nbx_option {
     /* 0 = fast (default): a_i = sum_j m_j d/(|d|^2+eps) with v_rcp_f32 + FMA, tile order,
      *     parity within the stated fp32 tolerance.
@@ -186,6 +186,21 @@ enum nbx_option {
                                     * bit-identical to 0.  Small blocks sum their pairs in another (fixed) order than the default
                                     * path: same bound, other bits; deterministic.  With L > 0 nbx_acc_jerk_subset uses the same
                                     * sweep for count <= 64 (nbx_last_launch: variant 42).  Anything else: NBX_ERR_INVALID */
+    NBX_OPT_LAW = 24,              /* the pair law of the all-pairs paths.  0 (default) = the reference's law, a 1/r force:
+                                    *   a_i = sum_j m_j d / s,   phi_i = sum_{j != i} m_j 1/2 ln s,   d = p_j - p_i, s = |d|^2 + eps;
+                                    * 1 = the Plummer-softened NEWTONIAN law with the same eps = 0.0001f (a softening length of 0.01):
+                                    *   a_i = sum_j m_j d s^(-3/2),   phi_i = -sum_{j != i} m_j s^(-1/2),
+                                    *   W = 1/2 sum_i m_i phi_i = -sum_{i<j} m_i m_j s^(-1/2)
+                                    * (z = 0 gives the same law in a plane).  With 1, nbx_step_brute_force, nbx_step_local,
+                                    * nbx_step_barnes_hut(theta == 0) and nbx_forces(theta == 0) run the packed sweep of
+                                    * force_newton.hip (nbx_last_launch: variant 30, or 31 when every mass is the same; it honours
+                                    * NBX_OPT_JSPLIT and NBX_OPT_DIM and ignores NBX_OPT_KERNEL_VARIANT; the kick-drift is unchanged),
+                                    * and nbx_forces_f64 / nbx_conserved its fp64 sibling (variant 65).  Everything else has no
+                                    * Newtonian form and returns NBX_ERR_STATE with the state untouched: Barnes-Hut steps and forces
+                                    * with theta != 0 (either tree dimension), the whole Hermite family, the bit-exact force mode,
+                                    * NBX_OPT_SOURCE_PRECISION = 16, a sharded engine (world > 1) and a member of an nbx_group.
+                                    * Changing the law discards the Hermite step's kept (a0, j0).  The six nb_* symbols always use
+                                    * law 0.  Anything but 0 or 1: NBX_ERR_INVALID */
     NBX_OPT_SOURCE_PRECISION = 6   /* 32 (default) or 16: all-pairs SOURCES read from a half4 (x,y,z,m) copy, 8 B/body;
                                     * targets, accumulators and the integrated state stay fp32 (fast mode only) */
 };
@@ -318,7 +333,9 @@ int32_t nbx_synchronize(nbx_engine *e);
 
 /* Force evaluation without state update, for parity tests on accelerations.
  * Writes F_i = m_i * a_i (the quantity nbody.rs:140-142 accumulates) for this engine's slab
- * targets; fz may be NULL. theta == 0 -> all-pairs, else Barnes-Hut traversal. cap >= slab size. */
+ * targets; fz may be NULL. theta == 0 -> all-pairs, else Barnes-Hut traversal. cap >= slab size.
+ * a_i follows NBX_OPT_LAW: sum_j m_j d / s by default, sum_j m_j d s^(-3/2) under the Newtonian law (theta == 0 only: a
+ * traversal under that law is NBX_ERR_STATE). */
 int32_t nbx_forces(nbx_engine *e, float theta, int32_t cap, float *fx, float *fy, float *fz);
 
 /* The fp64 arbiter on the device: all-pairs, double precision, whatever the force mode, NBX_OPT_DIM or the source precision say:
@@ -328,19 +345,24 @@ int32_t nbx_forces(nbx_engine *e, float theta, int32_t cap, float *fx, float *fy
  * modified.  Any output pointer may be NULL; phi == NULL skips the logarithm.  The pair j = i contributes nothing; distinct bodies
  * at one position contribute zero force and m_j * 1/2 ln(eps).  Deterministic: fixed reduction orders, no floating-point atomics.
  * Returns the slab size (cap >= slab size, else NBX_ERR_INVALID); NBX_ERR_NO_DEVICE without a GPU, NBX_ERR_STATE for a member of an
- * nbx_group.  nbx_last_launch afterwards: variant 64, jsplit = the source split, bodies_per_thread = targets per lane. */
+ * nbx_group.  nbx_last_launch afterwards: variant 64, jsplit = the source split, bodies_per_thread = targets per lane.
+ * NBX_OPT_LAW = 1 (Newtonian):   F_i = m_i * sum_{j != i} m_j d s^(-3/2),   phi_i = -sum_{j != i} m_j s^(-1/2),   s = |d|^2 + eps,
+ * by the sibling sweep (variant 65; the reciprocal square root refined to full double precision); phi == NULL skips the potential;
+ * distinct bodies at one position contribute zero force and -m_j / sqrt(eps).  Then also NBX_ERR_STATE in the bit-exact mode, with
+ * NBX_OPT_SOURCE_PRECISION = 16 and for a sharded engine. */
 int32_t nbx_forces_f64(nbx_engine *e, int32_t cap, double *fx, double *fy, double *fz, double *phi);
 
 enum nbx_conserved_id {
     NBX_CONS_KINETIC = 0,    /* sum 1/2 m |v|^2 */
-    NBX_CONS_POTENTIAL = 1,  /* 1/2 sum_{i in slab} m_i phi_i: over all ranks, sum_{i<j} 1/2 m_i m_j ln(|d|^2 + eps) */
+    NBX_CONS_POTENTIAL = 1,  /* 1/2 sum_{i in slab} m_i phi_i: over all ranks, sum_{i<j} 1/2 m_i m_j ln(|d|^2 + eps);
+                              * NBX_OPT_LAW = 1: W = -sum_{i<j} m_i m_j (|d|^2 + eps)^(-1/2) */
     NBX_CONS_MASS = 2,
     NBX_CONS_PX = 3, NBX_CONS_PY = 4, NBX_CONS_PZ = 5,      /* sum m v */
     NBX_CONS_LX = 6, NBX_CONS_LY = 7, NBX_CONS_LZ = 8,      /* sum m (r x v) */
     NBX_CONS_MRX = 9, NBX_CONS_MRY = 10, NBX_CONS_MRZ = 11, /* sum m r */
     NBX_CONS_COUNT = 12
 };
-/* The conserved sums of the 1/r law in fp64, on the device, over this engine's slab targets (world == 1: the whole system; a
+/* The conserved sums of the law NBX_OPT_LAW names (default: the 1/r law) in fp64, on the device, over this engine's slab targets (world == 1: the whole system; a
  * sharded caller adds its ranks' arrays).  count must be NBX_CONS_COUNT (else NBX_ERR_INVALID); out[nbx_conserved_id].  Runs the
  * sweep of nbx_forces_f64 with the potential; same statuses, same determinism, state untouched.  n == 0: all sums zero. */
 int32_t nbx_conserved(nbx_engine *e, int32_t count, double *out);

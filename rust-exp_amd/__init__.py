@@ -38,6 +38,9 @@ from .engine import (  # noqa: F401
     NBX_K_FORCE,
     NBX_K_INTEGRATE,
     NBX_K_TREE_BUILD,
+    NBX_LAW_NEWTON,
+    NBX_LAW_REFERENCE,
+    NBX_OPT_LAW,
     NBodyEngine,
     NBodyError,
     NBodyGroup,

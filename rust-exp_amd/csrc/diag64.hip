@@ -19,7 +19,9 @@
 //                 and taking it out again would cost a rounding of |m_i ln(eps)|, more than a sum of small terms allows -- so
 //                 the part of a wave's source range that meets the workgroup's own targets (at most 64 * T sources of the whole
 //                 sweep) runs a loop that predicates the potential on the index; every other source runs the plain loop.
-//   k_reduce64    per target: the S partials in ascending order, force times m_i, potential times 1/2 -> double4 (Fx, Fy, Fz, phi).
+//   k_newton64    the same sweep for the Newtonian law (NBX_OPT_LAW = 1; described where it stands).
+//   k_reduce64    per target: the S partials in ascending order, force times m_i, potential times 1/2 (times 1 under the Newtonian
+//                 law) -> double4 (Fx, Fy, Fz, phi).
 //   k_conserved64 the 12 sums of nbx_conserved_id: one body per thread, a fixed-order LDS tree per workgroup, then ONE workgroup
 //                 over the partials in index order.  Every product of two widened floats is exact in fp64.
 // Everything is deterministic: no atomics, every order fixed by the launch shape, which depends on (n, slab, CU count) only.
@@ -142,9 +144,117 @@ __global__ __launch_bounds__(kTile) void k_sweep64(const float4* __restrict__ po
     }
 }
 
+// K7's sibling for the Newtonian law (NBX_OPT_LAW = 1): F_i = m_i sum_j m_j d s^(-3/2), phi_i = -sum_{j != i} m_j s^(-1/2),
+// s = |d|^2 + eps.  K7's design unchanged -- k_widen64 records, T targets per lane, four waves splitting the source range and
+// meeting in LDS in wave order, sweep64_split / sweep64_stride, partial[S][stride] -- with another pair evaluation:
+//   u = s^(-1/2): v_rsq_f64, then TWO Newton steps y <- y + (y/2)(1 - (s y) y), each a multiply, an FMA for the residual, a multiply
+//   by 1/2 (exact) and an FMA.  A step squares the relative error (x 3/2): whatever the seed is good to beyond 2^-14, the second
+//   step leaves less than 2^-53 of it.  What remains are the roundings of the last step: the product s y (it enters the residual
+//   absolutely and u by half: 1/2) and the closing FMA (1) -- 3/2 roundings, charged as 2; s >= eps is always a normal number.
+//   m_j u^3 = (m_j u)(u u): three multiplies, then the three accumulating FMAs; 17 fp64 VALU instructions + 1 v_rsq_f64.
+//   POT: phi -= m_j u is ONE more FMA (K7 pays a library logarithm there).  The template is kept all the same: without the
+//   potential the kernel needs neither the accumulator nor the own-targets loop (the always-accumulating form was not measured).
+// The pair j = i: its force term is an exact zero, its potential term -m_i / sqrt(eps) is not and is predicated away by index in
+// the same "own targets" sub-range loop K7 uses.  Coincident distinct bodies contribute the finite -m_j / sqrt(eps).
+template <bool POT, bool SELF>
+__device__ __forceinline__ void newton_range(const double4* __restrict__ src64, const int ja, const int jb, Targets64& t)
+{
+    if (ja >= jb) return;
+    double4 next = src64[ja];
+#pragma unroll 2
+    for (int j = ja; j < jb; j++) {
+        const double4 s = next;
+        next = src64[j + 1 < jb ? j + 1 : j];   // the next record is on its way while this one is evaluated
+#pragma unroll
+        for (int k = 0; k < kT; k++) {
+            const double dx = s.x - t.x[k];
+            const double dy = s.y - t.y[k];
+            const double dz = s.z - t.z[k];
+            double r2 = __builtin_fma(dx, dx, kEps64);
+            r2 = __builtin_fma(dy, dy, r2);
+            r2 = __builtin_fma(dz, dz, r2);
+            double u = __builtin_amdgcn_rsq(r2);
+#pragma unroll
+            for (int step = 0; step < 2; step++) {
+                const double err = __builtin_fma(-(r2 * u), u, 1.0);
+                u = __builtin_fma(0.5 * u, err, u);
+            }
+            const double mu = s.w * u;
+            const double sc = mu * (u * u);
+            t.fx[k] = __builtin_fma(sc, dx, t.fx[k]);
+            t.fy[k] = __builtin_fma(sc, dy, t.fy[k]);
+            t.fz[k] = __builtin_fma(sc, dz, t.fz[k]);
+            if (POT) {
+                double w = s.w;
+                if (SELF) w = j == t.self[k] ? 0.0 : w;
+                t.ph[k] = __builtin_fma(-w, u, t.ph[k]);
+            }
+        }
+    }
+}
+
+template <bool POT>
+__global__ __launch_bounds__(kTile) void k_newton64(const float4* __restrict__ posm, const double4* __restrict__ src64, const int lo,
+                                                    const int n_targets, const int n_sources, const int stride,
+                                                    double4* __restrict__ partial)
+{
+    constexpr int kBlock = 64 * kT;          // targets per workgroup
+    constexpr int kAcc = POT ? 4 : 3;
+    __shared__ double red[4][kAcc][kBlock];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t0 = blockIdx.x * kBlock;
+    // this workgroup's source range, then this wave's quarter of it, exactly as k_sweep64 cuts them
+    const int base = n_sources / (int)gridDim.y, rem = n_sources % (int)gridDim.y, sy = (int)blockIdx.y;
+    const int j0 = sy * base + (sy < rem ? sy : rem), len = base + (sy < rem ? 1 : 0);
+    const int ja = j0 + (len >> 2) * wave + (wave < (len & 3) ? wave : (len & 3));
+    const int jb = ja + (len >> 2) + (wave < (len & 3) ? 1 : 0);
+    Targets64 t;
+#pragma unroll
+    for (int k = 0; k < kT; k++) {
+        int it = t0 + k * 64 + lane;
+        it = it < n_targets ? it : n_targets - 1;   // (idle lanes repeat the last target; nothing of theirs is written)
+        const float4 p = posm[lo + it];
+        t.x[k] = (double)p.x; t.y[k] = (double)p.y; t.z[k] = (double)p.z;
+        t.fx[k] = t.fy[k] = t.fz[k] = t.ph[k] = 0.0;
+        t.self[k] = lo + it;
+    }
+    if (POT) {
+        const int g0 = lo + t0, g1 = g0 + kBlock;   // sources that are this workgroup's own targets: bodies [g0, g1)
+        int sa = ja > g0 ? ja : g0, sb = jb < g1 ? jb : g1;
+        if (sa >= sb) sa = sb = jb;   // none: [ja, jb) and an empty range remain
+        newton_range<true, true>(src64, sa, sb, t);
+#pragma unroll 1
+        for (int part = 0; part < 2; part++) newton_range<true, false>(src64, part ? sb : ja, part ? jb : sa, t);
+    } else {
+        newton_range<false, false>(src64, ja, jb, t);
+    }
+#pragma unroll
+    for (int k = 0; k < kT; k++) {   // target k * 64 + lane of the block: conflict-free rows
+        red[wave][0][k * 64 + lane] = t.fx[k];
+        red[wave][1][k * 64 + lane] = t.fy[k];
+        red[wave][2][k * 64 + lane] = t.fz[k];
+        if (POT) red[wave][kAcc - 1][k * 64 + lane] = t.ph[k];
+    }
+    __syncthreads();
+    const int it = t0 + tid;
+    if (tid < kBlock && it < n_targets) {
+        double a[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int q = 0; q < kAcc; q++) {
+            a[q] = red[0][q][tid];
+#pragma unroll
+            for (int w = 1; w < 4; w++) a[q] += red[w][q][tid];
+        }
+        partial[(size_t)blockIdx.y * stride + it] = make_double4(a[0], a[1], a[2], a[3]);
+    }
+}
+
+// w_scale: what the summed .w is multiplied by -- 1/2 for K7's sum of m_j ln(s), 1 for the Newtonian -sum m_j / sqrt(s)
 __global__ __launch_bounds__(kTile) void k_reduce64(const float4* __restrict__ posm, const int lo, const int n_targets,
                                                     const double4* __restrict__ partial, const int split, const int stride,
-                                                    double4* __restrict__ out)
+                                                    double4* __restrict__ out, const double w_scale)
 {
     const int i = blockIdx.x * kTile + threadIdx.x;
     if (i >= n_targets) return;
@@ -154,7 +264,7 @@ __global__ __launch_bounds__(kTile) void k_reduce64(const float4* __restrict__ p
         a.x += q.x; a.y += q.y; a.z += q.z; a.w += q.w;
     }
     const double m = (double)posm[lo + i].w;
-    out[i] = make_double4(m * a.x, m * a.y, m * a.z, 0.5 * a.w);
+    out[i] = make_double4(m * a.x, m * a.y, m * a.z, w_scale * a.w);
 }
 
 constexpr int kCons = 12;        // NBX_CONS_COUNT
@@ -252,12 +362,25 @@ hipError_t launch_sweep64(const float4* posm, const double4* src64, int lo, int 
     return hipGetLastError();
 }
 
+hipError_t launch_newton64(const float4* posm, const double4* src64, int lo, int n_targets, int n_sources, int split, bool pot,
+                           double4* partial, hipStream_t stream, ForceLaunch* info)
+{
+    if (n_targets <= 0 || n_sources <= 0) return hipSuccess;
+    if (split < 1 || split > 65535) return hipErrorInvalidValue;
+    const int stride = sweep64_stride(n_targets);
+    const dim3 grid((unsigned)(stride / (64 * kT)), (unsigned)split);
+    if (info) *info = ForceLaunch{(int)(grid.x * grid.y), kTile, split, kT, 3, 65};
+    if (pot) hipLaunchKernelGGL(k_newton64<true>, grid, dim3(kTile), 0, stream, posm, src64, lo, n_targets, n_sources, stride, partial);
+    else     hipLaunchKernelGGL(k_newton64<false>, grid, dim3(kTile), 0, stream, posm, src64, lo, n_targets, n_sources, stride, partial);
+    return hipGetLastError();
+}
+
 hipError_t launch_reduce64(const float4* posm, int lo, int n_targets, const double4* partial, int split, double4* out,
-                           hipStream_t stream)
+                           hipStream_t stream, double w_scale)
 {
     if (n_targets <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_reduce64, dim3((n_targets + kTile - 1) / kTile), dim3(kTile), 0, stream, posm, lo, n_targets, partial,
-                       split, sweep64_stride(n_targets), out);
+                       split, sweep64_stride(n_targets), out, w_scale);
     return hipGetLastError();
 }
 

@@ -247,8 +247,43 @@ void choose_launch(const nbx_engine* e, int n_targets, int tiles_total, int* var
     *jsplit = s;
 }
 
+int newton_refusal(const nbx_engine* e)
+{
+    if (e->law != 1) return NBX_OK;
+    if (e->force_mode != 0) return fail(NBX_ERR_STATE, "NBX_OPT_LAW = 1: the Newtonian law has no bit-exact (strict) mode");
+    if (e->source_half) return fail(NBX_ERR_STATE, "NBX_OPT_LAW = 1: the Newtonian law reads fp32 sources (NBX_OPT_SOURCE_PRECISION = 16 is set)");
+    if (e->world > 1) return fail(NBX_ERR_STATE, "NBX_OPT_LAW = 1: the Newtonian law does not serve a sharded engine (world = %d)", e->world);
+    if (e->in_group) return fail(NBX_ERR_STATE, "NBX_OPT_LAW = 1: the Newtonian law does not serve an engine inside an nbx_group");
+    return NBX_OK;
+}
+
+int newton_unserved(const nbx_engine* e, const char* what)
+{
+    if (e->law != 1) return NBX_OK;
+    return fail(NBX_ERR_STATE, "NBX_OPT_LAW = 1: %s evaluates the reference's 1/r law only, not the Newtonian law", what);
+}
+
+// K11: the Newtonian sweep into e->d_acc.  One design for every size; NBX_OPT_JSPLIT and NBX_OPT_DIM are honoured,
+// NBX_OPT_KERNEL_VARIANT is not.  The unit-mass form only when EVERY mass is the same: K2's exceptions path is the 1/r law's
+static int launch_forces_newton(nbx_engine* e)
+{
+    const int slab = e->slab();
+    const int tiles_total = e->n_pad / kTile;
+    const int dim = e->dim_opt ? e->dim_opt : (e->any_z ? 3 : 2);
+    const int jsplit = nbx::newton_split(slab, tiles_total, e->cu_count, e->jsplit);
+    const int stride = ((slab + kTile - 1) / kTile) * kTile;
+    int rc = grow(&e->d_acc, &e->acc_cap, (size_t)jsplit * (size_t)std::max(stride, kTile));
+    if (rc != NBX_OK) return rc;
+    const bool unit = e->n > 0 && e->mass_min == e->mass_max;
+    ProfScope ps(e, NBX_K_FORCE);
+    HIP_TRY(nbx::launch_force_newton(e->d_posm, e->lo, slab, tiles_total, e->n, jsplit, dim, unit, e->mass_max, e->d_acc, stride,
+                                     e->stream, &e->last));
+    return NBX_OK;
+}
+
 int launch_forces_fast(nbx_engine* e)
 {
+    if (e->law == 1) return launch_forces_newton(e);
     const int slab = e->slab();
     const int tiles_total = e->n_pad / kTile;
     int variant, bpt, jsplit, dim;
@@ -310,6 +345,8 @@ bool log_enabled()
 
 int step_brute(nbx_engine* e, float dt)
 {
+    int nrc = newton_refusal(e);
+    if (nrc != NBX_OK) return nrc;
     e->positions_moved();   // (an all-pairs step moves every body: the order-sorted copy of the positions is stale from here)
     int rc = upload(e);
     if (rc != NBX_OK) return rc;

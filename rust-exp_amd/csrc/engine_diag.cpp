@@ -1,4 +1,4 @@
-// engine_diag.cpp -- host side of K7 (diag64.hip): nbx_forces_f64 and nbx_conserved.  Both read the live device state (posm, the
+// engine_diag.cpp -- host side of K7 and its Newtonian sibling (diag64.hip): nbx_forces_f64 and nbx_conserved.  Both read the live device state (posm, the
 // slab's velocities) and write workspaces of their own; nothing the stepping paths use is touched.
 #include "engine_internal.h"
 
@@ -17,6 +17,11 @@ static int sweep_f64(nbx_engine* e, bool pot)
     rc = grow(&e->d_out64, &e->out64_cap, (size_t)slab);
     if (rc != NBX_OK) return rc;
     HIP_TRY(nbx::launch_widen64(e->d_posm, e->d_src64, n, e->stream));
+    if (e->law == 1) {   // the Newtonian law: phi_i = -sum m_j / sqrt(s) needs no 1/2 (k_conserved64's 1/2 m_i phi_i is the pair energy)
+        HIP_TRY(nbx::launch_newton64(e->d_posm, e->d_src64, e->lo, slab, n, split, pot, e->d_part64, e->stream, &e->last));
+        HIP_TRY(nbx::launch_reduce64(e->d_posm, e->lo, slab, e->d_part64, split, e->d_out64, e->stream, 1.0));
+        return NBX_OK;
+    }
     HIP_TRY(nbx::launch_sweep64(e->d_posm, e->d_src64, e->lo, slab, n, split, pot, e->d_part64, e->stream, &e->last));
     HIP_TRY(nbx::launch_reduce64(e->d_posm, e->lo, slab, e->d_part64, split, e->d_out64, e->stream));
     return NBX_OK;
@@ -26,6 +31,8 @@ static int sweep_f64(nbx_engine* e, bool pot)
 static int diag_ready(nbx_engine* e)
 {
     if (e->in_group) return fail(NBX_ERR_STATE, "the fp64 sweep serves single engines, not members of an nbx_group");
+    const int nrc = newton_refusal(e);
+    if (nrc != NBX_OK) return nrc;
     return upload(e);
 }
 

@@ -16,6 +16,8 @@ int hermite_sweep_dim(const nbx_engine* e) { return e->dim_opt ? e->dim_opt : (e
 // step still in flight (ensure_device)
 int hermite_ready(nbx_engine* e)
 {
+    const int nrc = newton_unserved(e, "the Hermite family (its acceleration + jerk sweeps)");
+    if (nrc != NBX_OK) return nrc;
     int rc = ensure_device(e);
     if (rc != NBX_OK) return rc;
     if (e->world > 1) return fail(NBX_ERR_STATE, "the Hermite step serves unsharded engines: the other slabs' velocities are not on this rank");

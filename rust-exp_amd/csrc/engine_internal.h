@@ -248,6 +248,10 @@ struct nbx_engine {
 
     // options
     int force_mode = 0, jsplit = 0, bpt = 0, dim_opt = 0, profile = 0, variant = -1, strict_kernel = 0;
+    // NBX_OPT_LAW: 0 (default) = the reference's 1/r law of every kernel above, 1 = the Plummer-softened Newtonian law: K11
+    // (force_newton.hip) behind the all-pairs step and forces, k_newton64 behind nbx_forces_f64 / nbx_conserved; every other path
+    // refuses (newton_refusal / newton_unserved)
+    int law = 0;
     bool any_z = false;
     float mass_min = 0.0f, mass_max = 0.0f;   // over the current bodies (masses never change during a run)
     // "one common mass + a handful of exceptions" (the reference's own nb_stable_orbits: unit planets + a 1000-mass sun,
@@ -455,6 +459,11 @@ int download_positions(nbx_engine* e);
 int download_velocities(nbx_engine* e);
 void choose_launch(const nbx_engine* e, int n_targets, int tiles_total, int* variant, int* bpt, int* jsplit, int* dim);
 int launch_forces_fast(nbx_engine* e);
+// NBX_OPT_LAW = 1.  newton_refusal: NBX_OK, or the status of a configuration the Newtonian all-pairs paths do not serve (the bit-exact
+// mode, fp16 sources, a sharded engine, a member of a group); newton_unserved: the status for a path that has no Newtonian form at
+// all (`what` names it).  Both NBX_OK under law 0; text in nbx_last_error
+int newton_refusal(const nbx_engine* e);
+int newton_unserved(const nbx_engine* e, const char* what);
 bool log_enabled();   // NBX_LOG=1
 nbx::MassExceptions exceptions_of(const nbx_engine* e);
 nbx::SelfImage self_image_of(const nbx_engine* e);

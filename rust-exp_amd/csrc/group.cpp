@@ -550,6 +550,10 @@ int32_t nbx_group_get_particles3(nbx_group* g, int32_t cap, float* px, float* py
 int32_t nbx_group_step_brute_force(nbx_group* g, float dt)
 {
     if (!g) return fail(NBX_ERR_INVALID, "null group");
+    for (const nbx_engine* e : g->eng) {   // (NBX_OPT_LAW = 1 serves no group: said here, on the caller's thread)
+        const int nrc = newton_refusal(e);
+        if (nrc != NBX_OK) return nrc;
+    }
     if (g->fp32_stale && !group_wants_half_exchange(g)) {   // e.g. a bit-exact step after fp16-source steps: it reads fp32 sources
         const int rc = group_replicate_fp32(g);
         if (rc != NBX_OK) return rc;
@@ -566,6 +570,10 @@ int32_t nbx_group_step_barnes_hut(nbx_group* g, float theta, float dt, int32_t n
     if (!g) return fail(NBX_ERR_INVALID, "null group");
     if (theta == 0.0f) return nbx_group_step_brute_force(g, dt);   // nbody.rs:197-200
     if (nthreads <= 0) return fail(NBX_ERR_INVALID, "nthreads must be >= 1");
+    for (const nbx_engine* e : g->eng) {
+        const int nrc = newton_unserved(e, "the Barnes-Hut step (theta != 0)");
+        if (nrc != NBX_OK) return nrc;
+    }
     // tree replica per device, built once per step and shared; each device evaluates its slab
     int rc = group_replicate_fp32(g);   // the tree is built from, and the walk reads, fp32 positions
     if (rc != NBX_OK) return rc;

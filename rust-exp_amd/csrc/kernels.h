@@ -119,6 +119,13 @@ hipError_t launch_force_wave_split(const float4* posm, int lo, int n_targets, in
                                    bool unit_mass, float mass, float4* acc_partial, int acc_stride, hipStream_t stream,
                                    ForceLaunch* info, const int* exc_idx = nullptr, float4* exc_rec = nullptr, int exc_count = 0,
                                    const float4* widened = nullptr);
+// K11 (force_newton.hip, k_newton_pkw): the same feeding, mapping and partials for the Newtonian law a_i = sum m_j d s^(-3/2)
+// (NBX_OPT_LAW = 1).  unit_mass: EVERY body has mass `mass` (no exceptions: K2 gets the empty MassExceptions).  info->variant = 30
+// (general masses) / 31 (one common mass), bpt = 4.  acc_stride >= n_targets.
+hipError_t launch_force_newton(const float4* posm, int lo, int n_targets, int tiles_total, int n_sources, int jsplit, int dim,
+                               bool unit_mass, float mass, float4* acc_partial, int acc_stride, hipStream_t stream, ForceLaunch* info);
+// its source split: jsplit_opt if positive (NBX_OPT_JSPLIT), else chosen as choose_launch does for variants 6 / 7
+int newton_split(int n_targets, int tiles_total, int cu_count, int jsplit_opt);
 // widened[i] = float4(posh[i]) for i < count: the fp16 source copy as fp32 records, once per step (K4)
 hipError_t launch_widen_half(const void* posh, float4* widened, int count, hipStream_t stream);
 
@@ -174,9 +181,14 @@ int sweep64_stride(int n_targets);   // records per partial slab: the targets ro
 // posm[lo + t], t < n_targets; pot = false leaves the logarithm out (.w = 0)
 hipError_t launch_sweep64(const float4* posm, const double4* src64, int lo, int n_targets, int n_sources, int split, bool pot,
                           double4* partial, hipStream_t stream, ForceLaunch* info);
-// out[t] = (m_t * sum of the partials' xyz in ascending split order, 1/2 * sum of their w)
+// the Newtonian sibling (k_newton64): partial[s][t] = (sum m_j d s^(-3/2), -sum_{j != t} m_j s^(-1/2)), s = |d|^2 + eps; pot = false
+// leaves the potential out (.w = 0).  Same split, stride and partials as launch_sweep64; info->variant = 65
+hipError_t launch_newton64(const float4* posm, const double4* src64, int lo, int n_targets, int n_sources, int split, bool pot,
+                           double4* partial, hipStream_t stream, ForceLaunch* info);
+// out[t] = (m_t * sum of the partials' xyz in ascending split order, w_scale * sum of their w): 1/2 for launch_sweep64's sum of
+// m_j ln(s), 1 for launch_newton64's
 hipError_t launch_reduce64(const float4* posm, int lo, int n_targets, const double4* partial, int split, double4* out,
-                           hipStream_t stream);
+                           hipStream_t stream, double w_scale = 0.5);
 // the 12 sums of nbx_conserved_id over the slab into sums[0..12); workspace: conserved64_workspace(n_targets) doubles
 size_t conserved64_workspace(int n_targets);
 hipError_t launch_conserved64(const float4* posm, int lo, int n_targets, const float4* vel, const double4* out, double* workspace,

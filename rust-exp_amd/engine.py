@@ -41,6 +41,9 @@ NBX_OPT_BH_WALK = 18
 NBX_OPT_BH_FUSE_KICK = 20
 NBX_OPT_BH_DIM = 22              # (21 is not an option)
 NBX_OPT_HERMITE_BLOCK_TRAIN = 23
+NBX_OPT_LAW = 24
+NBX_LAW_REFERENCE = 0
+NBX_LAW_NEWTON = 1
 # (10-12 and 17 became enum nbx_stat in round 5; 16 and 19 -- measured losers -- were removed)
 
 NBX_STAT_BH_FALLBACKS = 0
@@ -427,6 +430,12 @@ class NBodyEngine:
     def set_mode(self, mode):
         self.set_option(NBX_OPT_FORCE_MODE, {"fast": 0, "strict": 1}[mode])
 
+    def set_law(self, law):
+        """The pair law of the all-pairs paths (NBX_OPT_LAW): "reference" (default) = the reference's 1/r force
+        a = sum m_j d / (|d|^2 + eps); "newton" = the Plummer-softened Newtonian a = sum m_j d (|d|^2 + eps)^(-3/2).  Under
+        "newton" the all-pairs steps, forces(0.0), forces_f64 and conserved serve the law; everything else raises NBX_ERR_STATE."""
+        self.set_option(NBX_OPT_LAW, {"reference": NBX_LAW_REFERENCE, "newton": NBX_LAW_NEWTON}[law])
+
     def get_option(self, opt):
         return int(self._L.nbx_get_option(self._h, opt))
 
@@ -521,7 +530,8 @@ class NBodyEngine:
 
     def forces_f64(self, potential=True):
         """The fp64 arbiter on the device (nbx_forces_f64): all-pairs F_i and phi_i = sum_j m_j 1/2 ln(|d|^2 + eps) of this
-        engine's slab as float64 arrays fx, fy, fz, phi; potential=False skips the logarithm and returns phi = None."""
+        engine's slab as float64 arrays fx, fy, fz, phi; potential=False skips the logarithm and returns phi = None.
+        Under set_law("newton"): F_i = m_i sum_j m_j d s^(-3/2) and phi_i = -sum_{j != i} m_j s^(-1/2), s = |d|^2 + eps."""
         lo, hi = self.slab()
         fx, fy, fz = (np.zeros(hi - lo, np.float64) for _ in range(3))
         phi = np.zeros(hi - lo, np.float64) if potential else None
@@ -529,7 +539,9 @@ class NBodyEngine:
         return fx, fy, fz, phi
 
     def conserved(self, count=NBX_CONS_COUNT):
-        """The conserved sums over this engine's slab in fp64 (nbx_conserved; a sharded caller adds its ranks' values)."""
+        """The conserved sums over this engine's slab in fp64 (nbx_conserved; a sharded caller adds its ranks' values).
+        "potential" is 1/2 sum m_i phi_i with forces_f64's phi: sum_{i<j} 1/2 m_i m_j ln(|d|^2 + eps) under the reference law,
+        W = -sum_{i<j} m_i m_j (|d|^2 + eps)^(-1/2) under set_law("newton")."""
         out = np.zeros(max(count, NBX_CONS_COUNT), np.float64)
         _check(self._L.nbx_conserved(self._h, count, _p(out)))
         return {"kinetic": float(out[NBX_CONS_KINETIC]), "potential": float(out[NBX_CONS_POTENTIAL]),
