@@ -386,6 +386,27 @@ int32_t nbx_step_hermite(nbx_engine *e, float dt);
  * contribute zero acceleration and the finite jerk m_j w / eps.  Leaves the evaluated pair as the kept (a0, j0): a Hermite step
  * that follows starts from it.  Statuses as nbx_step_hermite. */
 int32_t nbx_acc_jerk(nbx_engine *e, int32_t cap, float *ax, float *ay, float *az, float *jx, float *jy, float *jz);
+/* The fp64 arbiter of a_i and j_i on the device: all-pairs, double precision, for the law NBX_OPT_LAW names, whatever NBX_OPT_DIM,
+ * the force mode's kernels or NBX_OPT_BH_DIM say (always 3-D; z = 0 gives the planar law exactly), from the fp32 state widened
+ * exactly to fp64, eps = (double)0.0001f:
+ *   a_i = sum_j m_j d / s,   j_i = sum_j m_j ( w / s - 2 (d.w) d / s^2 ),   d = p_j - p_i, w = v_j - v_i, s = |d|^2 + eps
+ * NBX_OPT_LAW = 1 (Newtonian):   a_i = sum_j m_j d s^(-3/2),   j_i = sum_j m_j ( w s^(-3/2) - 3 (d.w) d s^(-5/2) )
+ * (the reciprocal and the reciprocal square root refined to full double precision).  Accelerations, not forces.  The pair j = i
+ * contributes exact zeros; distinct bodies at one position contribute zero acceleration and the finite jerk m_j w / eps
+ * (m_j w eps^(-3/2) under the Newtonian law).  idx == NULL: every body, count = the capacity (>= n, else NBX_ERR_INVALID), returns
+ * n.  idx != NULL: the `count` listed bodies in list order, duplicates allowed, returns count; an index outside [0, n) is
+ * NBX_ERR_INVALID.  count == 0 or n == 0 returns 0.  Any output pointer may be NULL.  The live device state is read (a Barnes-Hut
+ * step still in flight is resolved first) and never modified, and neither are the kept (a0, j0), the block levels or anything else
+ * the Hermite family holds: an integrator continues bit for bit as if the call had not been made.  Deterministic: fixed reduction
+ * orders, no atomics; the order of summation for a body depends on (n, the source split) only, so for one split a listed row is
+ * the full call's row of that body bit for bit.  NBX_OPT_JSPLIT sets the source split (0 = by the number of target blocks: a
+ * single listed body still occupies the GPU), NBX_OPT_BODIES_PER_THREAD the targets per lane (0 = by the number of targets; the
+ * results do not depend on it).  nbx_last_launch afterwards: variant 66 (67 under the Newtonian law), jsplit = the
+ * source split, bodies_per_thread = targets per lane.  NBX_ERR_NO_DEVICE without a GPU; NBX_ERR_STATE for a member of an nbx_group
+ * and for a sharded engine (the other slabs' velocities are not on the rank); under NBX_OPT_LAW = 1 also in the bit-exact mode and
+ * with NBX_OPT_SOURCE_PRECISION = 16.  The state is untouched in every case. */
+int32_t nbx_acc_jerk_f64(nbx_engine *e, const int32_t *idx, int32_t count, double *ax, double *ay, double *az, double *jx, double *jy,
+                         double *jz);
 /* The shared Aarseth-style step *dt_out = eta * min_i |a_i| / |j_i| over the kept (a0, j0), reduced on the device (evaluated
  * first if there is no valid pair).  Bodies with |j_i| = 0 are skipped; none left (or n == 0): +inf.  Statuses as above. */
 int32_t nbx_hermite_timestep(nbx_engine *e, float eta, float *dt_out);

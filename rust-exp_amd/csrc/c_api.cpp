@@ -485,6 +485,14 @@ int32_t nbx_conserved(nbx_engine* e, int32_t count, double* out)
     return conserved_f64(e, count, out);
 }
 
+// the fp64 acceleration + jerk sweep, both laws (K12: engine_acc_jerk64.cpp, acc_jerk64.hip)
+int32_t nbx_acc_jerk_f64(nbx_engine* e, const int32_t* idx, int32_t count, double* ax, double* ay, double* az, double* jx, double* jy,
+                         double* jz)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return acc_jerk_f64(e, idx, count, ax, ay, az, jx, jy, jz);
+}
+
 // the 4th-order Hermite step and its acceleration + jerk sweep (K8: engine_hermite.cpp, hermite.hip)
 int32_t nbx_step_hermite(nbx_engine* e, float dt)
 {

@@ -435,6 +435,10 @@ void free_device(nbx_engine* e)
     if (e->d_part64) (void)hipFree(e->d_part64);
     if (e->d_out64) (void)hipFree(e->d_out64);
     if (e->d_cons64) (void)hipFree(e->d_cons64);
+    if (e->d_aj64src) (void)hipFree(e->d_aj64src);
+    if (e->d_aj64part) (void)hipFree(e->d_aj64part);
+    if (e->d_aj64list) (void)hipFree(e->d_aj64list);
+    if (e->d_aj64out) (void)hipFree(e->d_aj64out);
     if (e->d_hsrc) (void)hipFree(e->d_hsrc);
     if (e->d_hpart) (void)hipFree(e->d_hpart);
     if (e->d_hkept) (void)hipFree(e->d_hkept);

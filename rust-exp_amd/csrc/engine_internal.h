@@ -207,6 +207,15 @@ struct nbx_engine {
     size_t out64_cap = 0;
     double* d_cons64 = nullptr;    // the 12 sums, then the workgroups' partials
     size_t cons64_cap = 0;
+    // K12, the fp64 acceleration + jerk sweep of nbx_acc_jerk_f64 (engine_acc_jerk64.cpp): workspaces only, rewritten by every call
+    nbx::AccJerk64Src* d_aj64src = nullptr;   // (posm, vel)[0..n) widened to 64-byte records
+    size_t aj64src_cap = 0;
+    nbx::AccJerk64* d_aj64part = nullptr;     // [split][stride] partial (a, j)
+    size_t aj64part_cap = 0;
+    int* d_aj64list = nullptr;                // the listed targets
+    size_t aj64list_cap = 0;
+    nbx::AccJerk64* d_aj64out = nullptr;      // (a, j) per slot
+    size_t aj64out_cap = 0;
     // K8, the Hermite step (engine_hermite.cpp): workspaces, and the one piece of state the integrator keeps between steps
     nbx::HermiteSrc* d_hsrc = nullptr;    // the sweep's source records: every body, predicted (n_pad records)
     size_t hsrc_cap = 0;
@@ -490,6 +499,8 @@ int oct_dump(nbx_engine* e, void* rows, int cap);
 // engine_diag.cpp: the fp64 all-pairs sweep (K7) on the live device state, which it never modifies
 int forces_f64(nbx_engine* e, int cap, double* fx, double* fy, double* fz, double* phi);
 int conserved_f64(nbx_engine* e, int count, double* out);
+// engine_acc_jerk64.cpp: the fp64 acceleration + jerk sweep (K12), both laws; idx == nullptr: every body (count = capacity)
+int acc_jerk_f64(nbx_engine* e, const int32_t* idx, int count, double* ax, double* ay, double* az, double* jx, double* jy, double* jz);
 // engine_hermite.cpp: the 4th-order Hermite step around the acceleration + jerk sweep (K8)
 int step_hermite(nbx_engine* e, float dt);
 int acc_jerk(nbx_engine* e, int cap, float* ax, float* ay, float* az, float* jx, float* jy, float* jz);

@@ -194,6 +194,31 @@ size_t conserved64_workspace(int n_targets);
 hipError_t launch_conserved64(const float4* posm, int lo, int n_targets, const float4* vel, const double4* out, double* workspace,
                               double* sums, hipStream_t stream);
 
+// ---- K12 (acc_jerk64.hip): the fp64 acceleration + jerk sweep behind nbx_acc_jerk_f64, both laws, all bodies or a list ----
+constexpr int kAccJerk64Targets = 2;   // T of the full sweep, targets per lane (1, 2 and 4 are built; the A/B is in docs/rounds/r13.md)
+// source (and target) record of the sweep: the body in doubles, 64 bytes = one 16-dword scalar load
+struct alignas(64) AccJerk64Src {
+    double x, y, z, m, vx, vy, vz, pad;
+};
+// (ax, ay, az, 0), (jx, jy, jz, 0): a partial sum of the sweep, or a slot's result
+struct alignas(64) AccJerk64 {
+    double4 a, j;
+};
+static_assert(sizeof(AccJerk64Src) == 64 && sizeof(AccJerk64) == 64, "layouts the kernels address as two double4");
+// src[i] = (posm[i], vel[i]) widened exactly, for i < n.  Unsharded engines only: vel holds all n bodies
+hipError_t launch_widen_aj64(const float4* posm, const float4* vel, AccJerk64Src* src, int n, hipStream_t stream);
+int acc_jerk64_targets(int n_targets);          // T for this many targets: kAccJerk64Targets, less for a list that would leave lanes idle
+int acc_jerk64_stride(int n_targets, int t);    // slots per partial slab: the targets rounded up to whole workgroups
+// the source split: jsplit_opt if positive (NBX_OPT_JSPLIT; at most n_sources), else from the number of target blocks -- four
+// workgroups per CU, however few the targets -- with every wave keeping 16 sources or more
+int acc_jerk64_split(int n_targets, int n_sources, int cu_count, int t, int jsplit_opt);
+// partial[s][slot] = (a, j) of target src[list[slot]] (list == nullptr: src[slot]), slot < n_targets, over the s-th of `split` ranges
+// of the n_sources records, under law 0 (1/r) or 1 (Newtonian); t = 1, 2 or 4.  info->variant = 66 + law, jsplit = split, bpt = t
+hipError_t launch_acc_jerk64(const AccJerk64Src* src, const int* list, int n_targets, int n_sources, int law, int split, int t,
+                             AccJerk64* partial, hipStream_t stream, ForceLaunch* info);
+// out[slot] = the partials of the slot in ascending split order
+hipError_t launch_reduce_aj64(int n_targets, const AccJerk64* partial, int split, int stride, AccJerk64* out, hipStream_t stream);
+
 // ---- K8 (hermite.hip): the acceleration + jerk sweep behind nbx_step_hermite / nbx_acc_jerk / nbx_hermite_timestep ----
 #ifndef NBX_HERMITE_T
 #define NBX_HERMITE_T 2   // (1 and 4 also build: the A/B of docs/rounds/r09.md compiled hermite.hip with -DNBX_HERMITE_T=...)

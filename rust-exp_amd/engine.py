@@ -228,6 +228,8 @@ def lib():
     L.nbx_conserved.restype = i32
     L.nbx_step_hermite.argtypes = [E, C.c_float]
     L.nbx_step_hermite.restype = i32
+    L.nbx_acc_jerk_f64.argtypes = [E, C.c_void_p, i32] + [C.c_void_p] * 6
+    L.nbx_acc_jerk_f64.restype = i32
     L.nbx_acc_jerk.argtypes = [E, i32] + [C.c_void_p] * 6
     L.nbx_acc_jerk.restype = i32
     L.nbx_hermite_timestep.argtypes = [E, C.c_float, C.POINTER(C.c_float)]
@@ -557,6 +559,17 @@ class NBodyEngine:
         n = self.num_particles()
         out = [np.zeros(n, np.float32) for _ in range(6)]
         _check(self._L.nbx_acc_jerk(self._h, n, *[_p(a) for a in out]))
+        return tuple(out)
+
+    def acc_jerk_f64(self, idx=None):
+        """The fp64 arbiter of acc_jerk on the device (nbx_acc_jerk_f64): ax, ay, az, jx, jy, jz as six float64 arrays, of every body
+        or of the listed ones in list order (duplicates allowed); state and kept pair untouched.  Under set_law("newton"):
+        a_i = sum_j m_j d s^(-3/2), j_i = sum_j m_j (w s^(-3/2) - 3 (d.w) d s^(-5/2)), s = |d|^2 + eps."""
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+        count = self.num_particles() if idx is None else len(idx)
+        out = [np.zeros(count, np.float64) for _ in range(6)]
+        _check(self._L.nbx_acc_jerk_f64(self._h, None if idx is None else _p(idx), count, *[_p(a) for a in out]))
         return tuple(out)
 
     def hermite_timestep(self, eta):
