@@ -176,6 +176,8 @@ enum nbx_option {
                                     * Fast mode on one unsharded engine with fp32 sources: the bit-exact mode, world > 1, an engine of
                                     * an nbx_group and NBX_OPT_SOURCE_PRECISION = 16 return NBX_ERR_STATE.  A root box so large that
                                     * two bodies further apart than EPS share a level-21 cell: NBX_ERR_TREE_DEPTH, state untouched.
+                                    * Under the Newtonian law (NBX_OPT_LAW) this path walks it (monopole + quadrupole of every accepted
+                                    * node, NBX_OPT_BH_QUADRUPOLE); the quadtree of 2 has no Newtonian form.
                                     * There is no "auto": the default never changes behaviour */
     NBX_OPT_HERMITE_BLOCK_TRAIN = 23, /* nbx_step_hermite_block: 0 (default) = every block step is the scheduler's four kernels, one
                                     * synchronous 8-byte read, predict, sweep, correct.  L = 1 .. 256: block steps of at most 64 due
@@ -195,12 +197,20 @@ enum nbx_option {
                                     * nbx_step_barnes_hut(theta == 0) and nbx_forces(theta == 0) run the packed sweep of
                                     * force_newton.hip (nbx_last_launch: variant 30, or 31 when every mass is the same; it honours
                                     * NBX_OPT_JSPLIT and NBX_OPT_DIM and ignores NBX_OPT_KERNEL_VARIANT; the kick-drift is unchanged),
-                                    * and nbx_forces_f64 / nbx_conserved its fp64 sibling (variant 65).  Everything else has no
+                                    * and nbx_forces_f64 / nbx_conserved its fp64 sibling (variant 65).  With NBX_OPT_BH_DIM = 3,
+                                    * nbx_step_barnes_hut and nbx_forces with theta != 0 walk the octree under this law: a leaf adds
+                                    * M x r^3 (x = c' - p, r = (|x|^2 + eps)^(-1/2)), an accepted interior node also the quadrupole of
+                                    * its second moment (NBX_OPT_BH_QUADRUPOLE).  Everything else has no
                                     * Newtonian form and returns NBX_ERR_STATE with the state untouched: Barnes-Hut steps and forces
-                                    * with theta != 0 (either tree dimension), the whole Hermite family, the bit-exact force mode,
+                                    * with theta != 0 on the quadtree (NBX_OPT_BH_DIM = 2), the whole Hermite family, the bit-exact force mode,
                                     * NBX_OPT_SOURCE_PRECISION = 16, a sharded engine (world > 1) and a member of an nbx_group.
                                     * Changing the law discards the Hermite step's kept (a0, j0).  The six nb_* symbols always use
                                     * law 0.  Anything but 0 or 1: NBX_ERR_INVALID */
+    NBX_OPT_BH_QUADRUPOLE = 25,    /* read only by the octree walk under NBX_OPT_LAW = 1.  1 (default): an accepted interior node adds
+                                    *   x (M r^3 - 1.5 tr(P) r^5 + 7.5 (x^T P x) r^7) - 3 r^5 (P x),
+                                    * P = sum_k m_k (r_k - c')(r_k - c')^T its second moment about its stored centre c' (the exact
+                                    * second-order term of the softened kernel; nbx_bh_oct_moments returns P); 0: M x r^3 alone, and the
+                                    * moments are not computed.  Leaves are evaluated alike.  Anything else: NBX_ERR_INVALID */
     NBX_OPT_SOURCE_PRECISION = 6   /* 32 (default) or 16: all-pairs SOURCES read from a half4 (x,y,z,m) copy, 8 B/body;
                                     * targets, accumulators and the integrated state stay fp32 (fast mode only) */
 };
@@ -335,7 +345,7 @@ int32_t nbx_synchronize(nbx_engine *e);
  * Writes F_i = m_i * a_i (the quantity nbody.rs:140-142 accumulates) for this engine's slab
  * targets; fz may be NULL. theta == 0 -> all-pairs, else Barnes-Hut traversal. cap >= slab size.
  * a_i follows NBX_OPT_LAW: sum_j m_j d / s by default, sum_j m_j d s^(-3/2) under the Newtonian law (theta == 0 only: a
- * traversal under that law is NBX_ERR_STATE). */
+ * traversal under that law is NBX_ERR_STATE, except the octree's: NBX_OPT_BH_DIM = 3). */
 int32_t nbx_forces(nbx_engine *e, float theta, int32_t cap, float *fx, float *fy, float *fz);
 
 /* The fp64 arbiter on the device: all-pairs, double precision, whatever the force mode, NBX_OPT_DIM or the source precision say:
@@ -455,6 +465,11 @@ int32_t nbx_bh_flat_dump(nbx_engine *e, void *rows, int32_t cap, int32_t threade
  * option says.  Pre-order, empty children dropped, 32-byte records {float px, py, pz, m; float s; int32 skip, interior, pad} with
  * s = the x-extent of the node's box.  Returns the node count; writes only when cap >= count. */
 int32_t nbx_bh_oct_dump(nbx_engine *e, void *rows, int32_t cap);
+/* Its second moments (what the Newtonian octree walk reads; geometry, so under either law): one row of 8 floats per node in the
+ * dump's order, (Pxx, Pyy, Pzz, Pxy, Pxz, Pyz, tr P, 0) of P = sum_k m_k (r_k - c')(r_k - c')^T about the node's dumped centre c',
+ * over its leaves as point masses at their dumped centres, accumulated in fp64 and rounded once; a leaf's row is zero.  Returns the
+ * node count; writes only when cap >= count. */
+int32_t nbx_bh_oct_moments(nbx_engine *e, float *rows, int32_t cap);
 
 /* ---- multi-GPU: bodies shard as contiguous slabs of targets, the reference's own thread split  */
 /* (range = N/world, last rank takes the remainder; nbody.rs:426-428).  One process per GPU; every */

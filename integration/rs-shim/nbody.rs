@@ -24,6 +24,8 @@ extern "C" {
                          vx: *const f32, vy: *const f32, m: *const f32) -> i32;
     fn nbx_get_particles(e: *mut NbxEngine, cap: i32, px: *mut f32, py: *mut f32,
                          vx: *mut f32, vy: *mut f32, m: *mut f32) -> i32;
+    // optional: the second moments of the octree's nodes (8 floats per node)
+    fn nbx_bh_oct_moments(e: *mut NbxEngine, rows: *mut f32, cap: i32) -> i32;
 }
 
 struct Engine(*mut NbxEngine);

@@ -40,6 +40,7 @@ from .engine import (  # noqa: F401
     NBX_K_TREE_BUILD,
     NBX_LAW_NEWTON,
     NBX_LAW_REFERENCE,
+    NBX_OPT_BH_QUADRUPOLE,
     NBX_OPT_LAW,
     NBodyEngine,
     NBodyError,

@@ -18,6 +18,7 @@
 //     origin, z origin 0, all three velocity components are zeroed) on its own bodies -- no other walk reads a body's position from
 //     the particle array, the records hold copies.  The forces-only form writes F = m a.
 // The loop is the compiler's schedule (a hand-scheduled one is a later A/B); this unit is built without the packed-fp32 instructions.
+#include "bh_oct_stack.h"
 #include "bh_threshold.h"
 #include "kernels.h"
 
@@ -27,7 +28,6 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v8f __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef unsigned long long u64;
 
 // ---- tree -> groups ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void oct_group_slot(const OctNode nd, const float theta, float4& rec, float& T, int& kid)
@@ -75,53 +75,6 @@ __global__ __launch_bounds__(kTile) void k_oct_groups(const OctNode* __restrict_
 }
 
 // ---- the walk ------------------------------------------------------------------------------------------------------------------
-constexpr int kOctSpill = 7 * kOctLevels - 64;   // entries beyond the 64 lanes
-
-__device__ __forceinline__ int oct_writelane(const int value, const int lane, int reg)
-{
-    // (VOP3 takes one SGPR: the lane select goes through m0)
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0" : "+v"(reg) : "s"(value), "s"(lane) : "m0");
-    return reg;
-}
-
-struct OctStack {
-    int g = 0, lo = 0, hi = 0;   // lanes = entries
-    int sp = 0;                  // wave-uniform
-    __device__ __forceinline__ void push(const int group, const u64 mask, volatile int* spill)
-    {
-        if (sp < 64) {
-            g = oct_writelane(group, sp, g);
-            lo = oct_writelane((int)(unsigned)mask, sp, lo);
-            hi = oct_writelane((int)(unsigned)(mask >> 32), sp, hi);
-        } else if (sp - 64 < kOctSpill) {
-            if (threadIdx.x == 0) {
-                spill[3 * (sp - 64) + 0] = group;
-                spill[3 * (sp - 64) + 1] = (int)(unsigned)mask;
-                spill[3 * (sp - 64) + 2] = (int)(unsigned)(mask >> 32);
-            }
-        }
-        sp++;
-    }
-    __device__ __forceinline__ void pop(int& group, u64& mask, volatile int* spill)
-    {
-        sp--;
-        int a, b, c;
-        if (sp < 64) {
-            a = __builtin_amdgcn_readlane(g, sp);
-            b = __builtin_amdgcn_readlane(lo, sp);
-            c = __builtin_amdgcn_readlane(hi, sp);
-        } else if (sp - 64 < kOctSpill) {
-            a = __builtin_amdgcn_readfirstlane(spill[3 * (sp - 64) + 0]);
-            b = __builtin_amdgcn_readfirstlane(spill[3 * (sp - 64) + 1]);
-            c = __builtin_amdgcn_readfirstlane(spill[3 * (sp - 64) + 2]);
-        } else {   // unreachable (see kOctSpill): an empty mask -- the record is loaded and nobody is inside
-            a = 0; b = 0; c = 0;
-        }
-        group = a;
-        mask = (u64)(unsigned)b | ((u64)(unsigned)c << 32);
-    }
-};
-
 // One child (slot c = record half G, quarter j): the lanes of M with "not (dist_sq <= T)" take it -- a NaN takes (and poisons the sum,
 // as in the reference) instead of opening; the pair law runs under their exec mask (the empty asm keeps the block a branch); the
 // other lanes of M open it: its record goes on the stack with their mask.

@@ -65,7 +65,8 @@ int32_t nbx_set_option(nbx_engine* e, int32_t option, int64_t value)
     switch (option) {   // a step that is still in flight was issued under the CURRENT options: settle it (and redo it, if its device
                         // build was refused) before any option that shapes a step changes
         case NBX_OPT_FORCE_MODE: case NBX_OPT_BH_TREE: case NBX_OPT_BH_FOLD: case NBX_OPT_BH_WAVE: case NBX_OPT_BH_ASYNC:
-        case NBX_OPT_SOURCE_PRECISION: case NBX_OPT_BH_WALK: case NBX_OPT_BH_FUSE_KICK: case NBX_OPT_BH_DIM: case NBX_OPT_LAW: {
+        case NBX_OPT_SOURCE_PRECISION: case NBX_OPT_BH_WALK: case NBX_OPT_BH_FUSE_KICK: case NBX_OPT_BH_DIM: case NBX_OPT_LAW:
+        case NBX_OPT_BH_QUADRUPOLE: {
             const int rc = resolve_pending(e);
             if (rc != NBX_OK) return rc;
             break;
@@ -147,6 +148,10 @@ int32_t nbx_set_option(nbx_engine* e, int32_t option, int64_t value)
             if (e->law != (int)value) e->hermite_valid = false;   // (a kept (a0, j0) belongs to the other law)
             e->law = (int)value;
             return NBX_OK;
+        case NBX_OPT_BH_QUADRUPOLE:
+            if (value != 0 && value != 1) return fail(NBX_ERR_INVALID, "bh quadrupole must be 1 (monopole + quadrupole) or 0 (monopole only)");
+            e->bh_quadrupole = (int)value;
+            return NBX_OK;
         case NBX_OPT_BH_FOLD:
             if (value != 0 && value != 1 && value != -1) return fail(NBX_ERR_INVALID, "bh fold must be 0 (exact sums), 1 (reference fold) or -1 (by size)");
             e->bh_fold = (int)value;
@@ -187,6 +192,7 @@ int64_t nbx_get_option(const nbx_engine* e, int32_t option)
         case NBX_OPT_BH_DIM: return e->bh_dim;
         case NBX_OPT_HERMITE_BLOCK_TRAIN: return e->hblock_train;
         case NBX_OPT_LAW: return e->law;
+        case NBX_OPT_BH_QUADRUPOLE: return e->bh_quadrupole;
         default: return NBX_ERR_INVALID;
     }
 }
@@ -228,7 +234,7 @@ int32_t nbx_query_option(const nbx_engine* e, int32_t option, int64_t* value)
         case NBX_OPT_FORCE_MODE: case NBX_OPT_JSPLIT: case NBX_OPT_BODIES_PER_THREAD: case NBX_OPT_DIM: case NBX_OPT_PROFILE:
         case NBX_OPT_KERNEL_VARIANT: case NBX_OPT_SOURCE_PRECISION: case NBX_OPT_DRAW_DEVICE: case NBX_OPT_BH_TREE: case NBX_OPT_BH_WAVE:
         case NBX_OPT_STRICT_KERNEL: case NBX_OPT_BH_FOLD: case NBX_OPT_BH_ASYNC: case NBX_OPT_BH_WALK: case NBX_OPT_BH_FUSE_KICK:
-        case NBX_OPT_BH_DIM: case NBX_OPT_HERMITE_BLOCK_TRAIN: case NBX_OPT_LAW:
+        case NBX_OPT_BH_DIM: case NBX_OPT_HERMITE_BLOCK_TRAIN: case NBX_OPT_LAW: case NBX_OPT_BH_QUADRUPOLE:
             if (value) *value = nbx_get_option(e, option);
             return NBX_OK;
         default:
@@ -367,7 +373,8 @@ int32_t nbx_step_barnes_hut(nbx_engine* e, float theta, float dt, int32_t nthrea
     // the reference spawns no worker and updates nobody for nthreads <= 0 (the division by it sits inside the closure of an
     // empty iterator, nbody.rs:424-428); level 2 reports the argument instead of silently doing nothing
     if (nthreads <= 0) return fail(NBX_ERR_INVALID, "nthreads must be >= 1 (the reference would update no particle)");
-    const int nrc = newton_unserved(e, "the Barnes-Hut step (theta != 0)");
+    // (the octree path has a Newtonian walk, bh_oct_newton.hip; the planar quadtree has none)
+    const int nrc = e->bh_dim == 3 ? newton_refusal(e) : newton_unserved(e, "the Barnes-Hut step (theta != 0)");
     if (nrc != NBX_OK) return nrc;
     return step_bh(e, theta, dt);
 }
@@ -393,7 +400,7 @@ int32_t nbx_forces(nbx_engine* e, float theta, int32_t cap, float* fx, float* fy
 {
     if (!e) return fail(NBX_ERR_INVALID, "null engine");
     const bool octree = theta != 0.0f && e->bh_dim == 3;   // (theta == 0: all-pairs, which honours z already)
-    int rc = theta != 0.0f ? newton_unserved(e, "the Barnes-Hut traversal (theta != 0)") : newton_refusal(e);
+    int rc = theta != 0.0f && !octree ? newton_unserved(e, "the Barnes-Hut traversal (theta != 0)") : newton_refusal(e);
     if (rc != NBX_OK) return rc;
     rc = octree ? bh3_refusal(e) : NBX_OK;
     if (rc != NBX_OK) return rc;
@@ -663,6 +670,12 @@ int32_t nbx_bh_oct_dump(nbx_engine* e, void* rows, int32_t cap)
 {
     if (!e) return fail(NBX_ERR_INVALID, "null engine");
     return oct_dump(e, rows, cap);
+}
+
+int32_t nbx_bh_oct_moments(nbx_engine* e, float* rows, int32_t cap)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return oct_moments(e, rows, cap);
 }
 
 // ---- checkpoint: the reference has none (state is lost on every experiment switch) ----

@@ -427,6 +427,9 @@ void free_device(nbx_engine* e)
     if (e->d_oct_ws) (void)hipFree(e->d_oct_ws);
     if (e->d_oct_nodes) (void)hipFree(e->d_oct_nodes);
     if (e->d_oct_groups) (void)hipFree(e->d_oct_groups);
+    if (e->d_oct_quads) (void)hipFree(e->d_oct_quads);
+    if (e->d_oct_mom) (void)hipFree(e->d_oct_mom);
+    if (e->d_oct_rows) (void)hipFree(e->d_oct_rows);
     if (e->h_oct_counters) (void)hipHostFree(e->h_oct_counters);
     if (e->d_guard) (void)hipFree(e->d_guard);
     if (e->d_exc_idx) (void)hipFree(e->d_exc_idx);

@@ -1,5 +1,6 @@
 // engine_bh3.cpp -- the 3-D Barnes-Hut path (NBX_OPT_BH_DIM = 3): octree built on the device (bh_oct.hip), walked once per wave
-// (bh_oct_walk.hip).  Step, forces-only evaluation and the dump of the tree.  The build is cold every step and the host reads the
+// (bh_oct_walk.hip; under NBX_OPT_LAW = 1 by bh_oct_newton.hip with the nodes' second moments).  Step, forces-only evaluation and the
+// dumps of the tree and its moments.  The build is cold every step and the host reads the
 // node count between its two halves (one small synchronous read); the gated asynchronous pipeline, the warm sort, the bit-exact
 // mode, sharded and group engines and the fp16 source copy of the quadtree path are not served here: NBX_ERR_STATE.
 #include "engine_internal.h"
@@ -59,7 +60,17 @@ static int oct_build(nbx_engine* e, int* n_nodes, int* n_leaves, int* depth, con
     return NBX_OK;
 }
 
-// build + groups + walk; kick: the walk ends the step, else F = m a into e->d_out4
+// the second moments of the interior nodes of the tree in e->d_oct_nodes into e->d_oct_mom (bh_oct_newton.hip)
+static int oct_moments_sweep(nbx_engine* e, int n_nodes, int interior, int depth)
+{
+    const int rc = grow(&e->d_oct_mom, &e->oct_mom_cap, nbx::oct_moments_bytes(interior));
+    if (rc != NBX_OK) return rc;
+    HIP_TRY(nbx::launch_oct_moments(e->d_oct_nodes, n_nodes, interior, depth, e->d_oct_mom, e->stream));
+    return NBX_OK;
+}
+
+// build + groups + walk; kick: the walk ends the step, else F = m a into e->d_out4.  Under NBX_OPT_LAW = 1: the moments and their
+// records behind the groups (unless NBX_OPT_BH_QUADRUPOLE = 0), then the Newtonian walk
 static int oct_evaluate(nbx_engine* e, float theta, bool kick, float dt, int* n_nodes, int* depth)
 {
     int leaves = 0;
@@ -73,8 +84,22 @@ static int oct_evaluate(nbx_engine* e, float theta, bool kick, float dt, int* n_
         rc = grow(&e->d_out4, &e->out4_cap, (size_t)e->n);
         if (rc != NBX_OK) return rc;
     }
+    const bool quad = e->law == 1 && e->bh_quadrupole != 0;
+    if (quad) {
+        rc = grow(&e->d_oct_quads, &e->oct_quads_cap, records + records / 8);
+        if (rc != NBX_OK) return rc;
+        ProfScope ps(e, NBX_K_TREE_BUILD);
+        rc = oct_moments_sweep(e, *n_nodes, *n_nodes - leaves, *depth);
+        if (rc != NBX_OK) return rc;
+        HIP_TRY(nbx::launch_oct_quads(e->d_oct_nodes, *n_nodes, *n_nodes - leaves, e->d_oct_mom, e->d_oct_quads, e->stream));
+    }
     ProfScope ps(e, NBX_K_BH_EVAL);
     HIP_TRY(nbx::launch_oct_groups(e->d_oct_nodes, *n_nodes, theta, e->d_oct_groups, e->stream));
+    if (e->law == 1) {
+        HIP_TRY(nbx::launch_oct_walk_newton(e->d_posm, e->n, order, e->d_oct_groups, quad ? e->d_oct_quads : nullptr,
+                                            kick ? nullptr : e->d_out4, kick ? e->d_vel : nullptr, dt, e->stream));
+        return NBX_OK;
+    }
     HIP_TRY(nbx::launch_oct_walk(e->d_posm, e->n, order, e->d_oct_groups, kick ? nullptr : e->d_out4, kick ? e->d_vel : nullptr, dt, e->stream));
     return NBX_OK;
 }
@@ -96,8 +121,8 @@ int step_bh3(nbx_engine* e, float theta, float dt)
     e->host_pos_valid = false;
     e->host_vel_valid = false;
     if (log_enabled())
-        std::fprintf(stderr, "[nbx] step_barnes_hut dev=%d n=%d theta=%g dt=%g mode=fast dim=3 tree=device nodes=%d depth=%d walk=wave\n",
-                     e->device, e->n, (double)theta, (double)dt, nodes, depth);
+        std::fprintf(stderr, "[nbx] step_barnes_hut dev=%d n=%d theta=%g dt=%g mode=fast dim=3 tree=device nodes=%d depth=%d walk=wave law=%d quad=%d\n",
+                     e->device, e->n, (double)theta, (double)dt, nodes, depth, e->law, e->law == 1 && e->bh_quadrupole != 0 ? 1 : 0);
     return NBX_OK;
 }
 
@@ -136,6 +161,29 @@ int oct_dump(nbx_engine* e, void* rows, int cap)
     rc = oct_build(e, &nodes, &leaves, &depth, nullptr);
     if (rc != NBX_OK) return rc;
     if (rows && cap >= nodes) HIP_TRY(hipMemcpyAsync(rows, e->d_oct_nodes, sizeof(nbx::OctNode) * (size_t)nodes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return nodes;
+}
+
+int oct_moments(nbx_engine* e, float* rows, int cap)
+{
+    if (e->n > kOctMaxBodies) return fail(NBX_ERR_STATE, "octree: more than %d bodies", kOctMaxBodies);
+    int rc = resolve_pending(e);
+    if (rc != NBX_OK) return rc;
+    rc = upload(e);
+    if (rc != NBX_OK) return rc;
+    if (e->n == 0) return 0;
+    int nodes = 0, leaves = 0, depth = 0;
+    rc = oct_build(e, &nodes, &leaves, &depth, nullptr);
+    if (rc != NBX_OK) return rc;
+    if (rows && cap >= nodes) {
+        rc = oct_moments_sweep(e, nodes, nodes - leaves, depth);
+        if (rc != NBX_OK) return rc;
+        rc = grow(&e->d_oct_rows, &e->oct_rows_cap, 8 * (size_t)nodes);
+        if (rc != NBX_OK) return rc;
+        HIP_TRY(nbx::launch_oct_moment_rows(e->d_oct_nodes, nodes, nodes - leaves, e->d_oct_mom, e->d_oct_rows, e->stream));
+        HIP_TRY(hipMemcpyAsync(rows, e->d_oct_rows, sizeof(float) * 8 * (size_t)nodes, hipMemcpyDeviceToHost, e->stream));
+    }
     HIP_TRY(hipStreamSynchronize(e->stream));
     return nodes;
 }

@@ -125,6 +125,15 @@ struct nbx_engine {
     nbx::OctGroup* d_oct_groups = nullptr;
     size_t oct_groups_cap = 0;
     int* h_oct_counters = nullptr; // pinned: nodes, leaves, leaves wider than EPS, depth of the last octree build
+    // NBX_OPT_LAW = 1 on the octree path (K13, bh_oct_newton.hip): the second moments of the interior nodes, their records beside
+    // d_oct_groups, and NBX_OPT_BH_QUADRUPOLE: 1 (default) = the walk adds the quadrupole of an accepted node, 0 = monopole only
+    int bh_quadrupole = 1;
+    char* d_oct_mom = nullptr;     // moments workspace (nbx::oct_moments_bytes)
+    size_t oct_mom_cap = 0;
+    nbx::OctQuad* d_oct_quads = nullptr;
+    size_t oct_quads_cap = 0;
+    float* d_oct_rows = nullptr;   // nbx_bh_oct_moments: 8 floats per node
+    size_t oct_rows_cap = 0;
     int bh_wave = 1;               // wave-uniform traversal when a spatial body order is available
     // A Barnes-Hut step on the device tree is enqueued WITHOUT waiting for the build's verdict (node count, EPS clusters): walk
     // and kick-drift are gated on the device by the build's own counters.  The host reads the verdict at the next call that
@@ -259,7 +268,7 @@ struct nbx_engine {
     int force_mode = 0, jsplit = 0, bpt = 0, dim_opt = 0, profile = 0, variant = -1, strict_kernel = 0;
     // NBX_OPT_LAW: 0 (default) = the reference's 1/r law of every kernel above, 1 = the Plummer-softened Newtonian law: K11
     // (force_newton.hip) behind the all-pairs step and forces, k_newton64 behind nbx_forces_f64 / nbx_conserved; every other path
-    // refuses (newton_refusal / newton_unserved)
+    // refuses (newton_refusal / newton_unserved), except the octree path (NBX_OPT_BH_DIM = 3), which walks it with K13
     int law = 0;
     bool any_z = false;
     float mass_min = 0.0f, mass_max = 0.0f;   // over the current bodies (masses never change during a run)
@@ -496,6 +505,7 @@ int bh3_refusal(const nbx_engine* e);   // NBX_OK, or the status of a configurat
 int step_bh3(nbx_engine* e, float theta, float dt);
 int forces_bh3(nbx_engine* e, float theta, float* fx, float* fy, float* fz);
 int oct_dump(nbx_engine* e, void* rows, int cap);
+int oct_moments(nbx_engine* e, float* rows, int cap);   // one 8-float row per node of oct_dump's order (either law)
 // engine_diag.cpp: the fp64 all-pairs sweep (K7) on the live device state, which it never modifies
 int forces_f64(nbx_engine* e, int cap, double* fx, double* fy, double* fz, double* phi);
 int conserved_f64(nbx_engine* e, int count, double* out);

@@ -97,6 +97,28 @@ hipError_t launch_oct_groups(const OctNode* nodes, int n_nodes, float theta, Oct
 hipError_t launch_oct_walk(float4* posm, int n, const unsigned* order, const OctGroup* groups, float4* forces, float4* kick_vel,
                            float dt, hipStream_t stream);
 
+// ---- K13: the octree under the Newtonian law (NBX_OPT_LAW = 1, bh_oct_newton.hip): second moments and the walk that uses them ----
+// The second moment of an interior node about its STORED fp32 centre c', P = sum_k m_k (r_k - c')(r_k - c')^T over the node's leaves
+// taken as point masses at their stored centres (a multi-body leaf has its bodies within EPS on every axis: a point, its own P = 0).
+// One OctQuad per OctGroup record at the same index, slots filled as k_oct_groups fills c[]: 8 children x (Pxx, Pyy, Pzz, Pxy, Pxz,
+// Pyz, tr P, 0) in fp32, so that one child's moments are a single 8-dword scalar load; leaves and absent slots are zero.
+struct alignas(64) OctQuad {
+    float q[8][8];
+};
+static_assert(sizeof(OctQuad) == 256, "layout shared with the kernels");
+constexpr int kOctMomDoubles = 10;   // per interior node (by rank), fp64: first moment D (3), P (xx yy zz xy xz yz) about c', mass
+// bytes of the moments workspace for `interior` interior nodes: node of every rank, completion stamps, the fp64 moments
+size_t oct_moments_bytes(int interior);
+// bottom-up, deterministic, no atomics: `depth` sweeps (counters[3]) over the interior nodes; a node's result does not depend on
+// scheduling.  Then launch_oct_quads files them as records; launch_oct_moment_rows as one 8-float row per node in pre-order
+hipError_t launch_oct_moments(const OctNode* nodes, int n_nodes, int interior, int depth, void* workspace, hipStream_t stream);
+hipError_t launch_oct_quads(const OctNode* nodes, int n_nodes, int interior, const void* workspace, OctQuad* quads, hipStream_t stream);
+hipError_t launch_oct_moment_rows(const OctNode* nodes, int n_nodes, int interior, const void* workspace, float* rows, hipStream_t stream);
+// launch_oct_walk's sibling for the Newtonian law: a += M x r^3 for a leaf, + the quadrupole term of an accepted interior node
+// when quads != nullptr (monopole only, and no OctQuad read, when it is null)
+hipError_t launch_oct_walk_newton(float4* posm, int n, const unsigned* order, const OctGroup* groups, const OctQuad* quads,
+                                  float4* forces, float4* kick_vel, float dt, hipStream_t stream);
+
 struct ForceLaunch {
     int grid, block, jsplit, bpt, dim, variant;
 };

@@ -42,6 +42,7 @@ NBX_OPT_BH_FUSE_KICK = 20
 NBX_OPT_BH_DIM = 22              # (21 is not an option)
 NBX_OPT_HERMITE_BLOCK_TRAIN = 23
 NBX_OPT_LAW = 24
+NBX_OPT_BH_QUADRUPOLE = 25
 NBX_LAW_REFERENCE = 0
 NBX_LAW_NEWTON = 1
 # (10-12 and 17 became enum nbx_stat in round 5; 16 and 19 -- measured losers -- were removed)
@@ -252,6 +253,8 @@ def lib():
     L.nbx_bh_flat_dump.restype = i32
     L.nbx_bh_oct_dump.argtypes = [E, C.c_void_p, i32]
     L.nbx_bh_oct_dump.restype = i32
+    L.nbx_bh_oct_moments.argtypes = [E, _f32p, i32]
+    L.nbx_bh_oct_moments.restype = i32
     L.nbx_set_shard.argtypes = [E, i32, i32]
     L.nbx_set_shard.restype = i32
     L.nbx_get_slab.argtypes = [E, C.POINTER(i32), C.POINTER(i32)]
@@ -435,7 +438,8 @@ class NBodyEngine:
     def set_law(self, law):
         """The pair law of the all-pairs paths (NBX_OPT_LAW): "reference" (default) = the reference's 1/r force
         a = sum m_j d / (|d|^2 + eps); "newton" = the Plummer-softened Newtonian a = sum m_j d (|d|^2 + eps)^(-3/2).  Under
-        "newton" the all-pairs steps, forces(0.0), forces_f64 and conserved serve the law; everything else raises NBX_ERR_STATE."""
+        "newton" the all-pairs steps, forces(0.0), forces_f64 and conserved serve the law, and with set_bh_dim(3) the octree's
+        step_barnes_hut / forces(theta) (monopole + quadrupole, set_bh_quadrupole); everything else raises NBX_ERR_STATE."""
         self.set_option(NBX_OPT_LAW, {"reference": NBX_LAW_REFERENCE, "newton": NBX_LAW_NEWTON}[law])
 
     def get_option(self, opt):
@@ -624,8 +628,14 @@ class NBodyEngine:
         self.set_option(NBX_OPT_BH_FOLD, {"exact": 0, "reference": 1, "auto": -1}[how])
 
     def set_bh_dim(self, dim):
-        """2 (default): Barnes-Hut on the quadtree of (x, y), z ignored; 3: the octree path (fast mode, one unsharded engine)."""
+        """2 (default): Barnes-Hut on the quadtree of (x, y), z ignored; 3: the octree path (fast mode, one unsharded engine), which
+        also serves set_law("newton")."""
         self.set_option(NBX_OPT_BH_DIM, dim)
+
+    def set_bh_quadrupole(self, on=True):
+        """The octree walk under set_law("newton"): True (default) adds the quadrupole of every accepted interior node, False
+        evaluates its monopole alone (NBX_OPT_BH_QUADRUPOLE).  Read by nothing else."""
+        self.set_option(NBX_OPT_BH_QUADRUPOLE, 1 if on else 0)
 
     def set_draw_device(self, on=True):
         """True / False force the device / host draw; None = by size (the default)."""
@@ -659,6 +669,15 @@ class NBodyEngine:
         cnt = _check(self._L.nbx_bh_oct_dump(self._h, None, 0))
         rows = np.zeros(max(cnt, 1), dt)
         cnt = _check(self._L.nbx_bh_oct_dump(self._h, _p(rows), cnt))
+        return rows[:cnt]
+
+    def bh_oct_moments(self):
+        """The second moments of bh_oct_dump's nodes, row for row, as a structured array (xx, yy, zz, xy, xz, yz, tr, pad):
+        P = sum m_k (r_k - c')(r_k - c')^T about the node's dumped centre over its leaves as points; zero rows for leaves."""
+        dt = np.dtype([(k, "<f4") for k in ("xx", "yy", "zz", "xy", "xz", "yz", "tr", "pad")])
+        cnt = _check(self._L.nbx_bh_oct_moments(self._h, None, 0))
+        rows = np.zeros(max(cnt, 1), dt)
+        cnt = _check(self._L.nbx_bh_oct_moments(self._h, rows.ctypes.data_as(_f32p), cnt))
         return rows[:cnt]
 
     # sharding
