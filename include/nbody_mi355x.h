@@ -384,7 +384,8 @@ int32_t nbx_conserved(nbx_engine *e, int32_t count, double *out);
  *   evaluate  (a1, j1) at (xp, vp): one sweep that computes both
  *   correct   v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12,   x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12
  * and (a1, j1) is kept on the device as the next step's (a0, j0).  Anything else that can change positions, velocities or masses
- * -- new particles, nbx_load, any other step, nbx_positions_device, a change of NBX_OPT_DIM -- discards the kept pair, and the
+ * -- new particles, nbx_load, any other step, nbx_positions_device, nbx_set_stream, setting NBX_OPT_DIM, a change of NBX_OPT_LAW --
+ * discards the kept pair (calls that only return data, nbx_forces with a tree build among them, and refused calls do not), and the
  * next Hermite step first evaluates it at the current state (one more sweep).  No velocity kill box.  Asynchronous on the engine's
  * stream, like the other steps; deterministic (fixed reduction orders, no atomics).  NBX_OPT_JSPLIT sets the source split (0 =
  * by size).  nbx_last_launch afterwards: variant 40, jsplit = the source split, bodies_per_thread = targets per lane.

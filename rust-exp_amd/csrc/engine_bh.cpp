@@ -201,8 +201,10 @@ int build_tree_on_device_begin(nbx_engine* e, int* host_counters, bool publish_b
                                          publish_by_kernel ? nullptr : (host_counters ? host_counters : e->h_counters), &e->d_perm,
                                          e->stream, fold, e->side_stream, e->ev_side_go, e->ev_side_done,
                                          /*depth_panic_guard=*/e->force_mode != 0, warm, warm ? e->sorted_positions() : nullptr));
-    e->positions_moved();    // the workspace holds a NEW order now: the order-sorted copy of the positions belongs to the old one
-                             // (the fused kick-drift of the step this build serves, if there is one, leaves a current copy again)
+    e->sorted_pos_valid = false;   // the workspace holds a NEW order now: the order-sorted copy of the positions belongs to the old one
+                                   // (the fused kick-drift of the step this build serves, if there is one, leaves a current copy again).
+                                   // Nothing has moved: a build that serves a read-only call (nbx_forces, the device tree dump) leaves
+                                   // the kept (a0, j0) of the Hermite family alone; a step's own kick-drift takes them back
     e->sort_warm_n = e->n;   // (a refusal -- of this build, or of one whose verdict is still in flight -- takes it back)
     return NBX_OK;
 }
@@ -301,7 +303,7 @@ int spatial_order(nbx_engine* e)
     // leaves a non-permutation; the device build's gate catches that, this path has no gate.  The sort overlaps the host build
     // (milliseconds), so nothing is lost; its order is still a good sampling frame for the next warm DEVICE build.
     HIP_TRY(nbx::device_spatial_order(e->d_posm, e->n, e->d_tree_ws, e->tree_ws_bytes, &e->d_perm, e->stream, /*warm=*/false, nullptr));
-    e->positions_moved();    // (as in build_tree_on_device_begin: a new order)
+    e->sorted_pos_valid = false;   // (as in build_tree_on_device_begin: a new order, and nothing moved)
     e->sort_warm_n = e->n;
     return NBX_OK;
 }

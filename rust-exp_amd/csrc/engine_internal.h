@@ -71,8 +71,9 @@ struct nbx_engine {
     float4* d_sorted_pos = nullptr;     // the positions in the order d_perm names, as the last fused kick-drift left them (BhKick::sorted)
     size_t sorted_pos_cap = 0;
     bool sorted_pos_valid = false;      // ... and whether they still ARE the current positions in that order: set by the launch of a
-                                        // fused walk + kick-drift, taken back by everything else that moves bodies on the device or
-                                        // replaces the order (positions_moved()); never with a bound positions buffer or world > 1
+                                        // fused walk + kick-drift, taken back by everything else that moves bodies on the device
+                                        // (positions_moved()) or replaces the order (a tree build, which moves nothing and so leaves
+                                        // hermite_valid alone); never with a bound positions buffer or world > 1
     void positions_moved() { sorted_pos_valid = false; hermite_valid = false; }   // (... and the kept (a0, j0) of the Hermite step)
     const float4* sorted_positions() const { return (sorted_pos_valid && world == 1 && !posm_external && sort_warm_n == n) ? d_sorted_pos : nullptr; }
     int sort_warm_n = 0;                // > 0: the tree workspace holds the sorted order of this many bodies as of the last build /

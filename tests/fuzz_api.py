@@ -3,7 +3,9 @@
     python tests/fuzz_api.py [first_seed] [count]
 Random sequences of set_particles (sizes change), brute-force / Barnes-Hut steps, forces, draw, get_particles, option
 flips (tree on host/device -- ignored by the bit-exact mode --, shared walk on/off, mode fast<->strict and back),
-checkpoint save/load; the oracle runs the same sequence and every observable must match bit for bit."""
+checkpoint save/load; the oracle runs the same sequence and every observable must match bit for bit.
+The fast-mode features (octree, Newtonian law, fp64 diagnostics, Hermite family) have their sequences in
+tests/test_gpu_mixed_sequences.py, which pytest collects: replay against a fresh engine instead of the oracle."""
 import os
 import sys
 import tempfile
