@@ -471,6 +471,29 @@ int32_t nbx_bh_oct_dump(nbx_engine *e, void *rows, int32_t cap);
  * over its leaves as point masses at their dumped centres, accumulated in fp64 and rounded once; a leaf's row is zero.  Returns the
  * node count; writes only when cap >= count. */
 int32_t nbx_bh_oct_moments(nbx_engine *e, float *rows, int32_t cap);
+/* The potential of ONE octree walk under the Newtonian law (NBX_OPT_BH_DIM = 3 and NBX_OPT_LAW = 1, else NBX_ERR_STATE naming the
+ * option): the tree of the current state is built as for nbx_forces(theta), every body walks it with the same opening decisions,
+ * and with x = c' - p, u = |x|^2 + eps, r = u^(-1/2) a taken child adds
+ *   a leaf, and every taken child with NBX_OPT_BH_QUADRUPOLE = 0:   -M r
+ *   an interior node:                                               -M r + 0.5 tr(P) r^3 - 1.5 (x^T P x) r^5
+ * (the second-order term of -m (|x + delta|^2 + eps)^(-1/2) with the raw second moment P of nbx_bh_oct_moments; its gradient is the
+ * force walk's formula).  phi_i follows nbx_forces_f64's convention, j = i excluded: the walk meets the body's own leaf like any
+ * other and m_i / sqrt(eps) is added back once.  For a body of a multi-body leaf (bodies within EPS of each other on every axis,
+ * merged by the build) that takes its offset from the leaf's centre as zero: its own share is wrong by at most |x|^2 / (2 eps) of
+ * itself, i.e. 1.5e-4 * 100 m_i -- the leaf merge's own approximation.  fp32, deterministic (one accumulator per body, fixed
+ * order).  Writes phi[i] for every body in body order (phi may be NULL); cap >= n, else NBX_ERR_INVALID; returns n (0 for an empty
+ * system).  theta must be finite and > 0 (NBX_ERR_INVALID: nbx_forces_f64 and nbx_conserved give the all-pairs answer).  Refused
+ * with NBX_ERR_STATE wherever the octree path is: the bit-exact mode, a sharded engine, a member of an nbx_group,
+ * NBX_OPT_SOURCE_PRECISION = 16.  NBX_ERR_TREE_DEPTH and NBX_ERR_TREE are the build's; NBX_ERR_NO_DEVICE without a GPU.  Read-only
+ * as nbx_forces is: positions, velocities, the kept Hermite pair, the block levels and the quadtree's warm order are untouched, and
+ * a step after the call is the step without it, bit for bit. */
+int32_t nbx_bh_potential(nbx_engine *e, float theta, int32_t cap, float *phi);
+/* The twelve sums of nbx_conserved with out[NBX_CONS_POTENTIAL] = 1/2 sum_i m_i phi_i over the phi of nbx_bh_potential(theta), each
+ * phi_i widened to double and the sums made by nbx_conserved's own reduction (the other eleven entries are nbx_conserved's bit for
+ * bit): W of a large system in one tree walk instead of an all-pairs fp64 sweep, to the accuracy of the walk.  count must be
+ * NBX_CONS_COUNT and out non-null (else NBX_ERR_INVALID); other statuses and the untouched state as nbx_bh_potential.  n == 0: all
+ * sums zero. */
+int32_t nbx_bh_conserved(nbx_engine *e, float theta, int32_t count, double *out);
 
 /* ---- multi-GPU: bodies shard as contiguous slabs of targets, the reference's own thread split  */
 /* (range = N/world, last rank takes the remainder; nbody.rs:426-428).  One process per GPU; every */

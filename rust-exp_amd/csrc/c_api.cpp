@@ -678,6 +678,19 @@ int32_t nbx_bh_oct_moments(nbx_engine* e, float* rows, int32_t cap)
     return oct_moments(e, rows, cap);
 }
 
+// the potential of the Newtonian octree walk and the conserved sums made from it (K14: engine_bh3.cpp, bh_oct_potential.hip)
+int32_t nbx_bh_potential(nbx_engine* e, float theta, int32_t cap, float* phi)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return potential_bh3(e, theta, cap, phi);
+}
+
+int32_t nbx_bh_conserved(nbx_engine* e, float theta, int32_t count, double* out)
+{
+    if (!e) return fail(NBX_ERR_INVALID, "null engine");
+    return conserved_bh3(e, theta, count, out);
+}
+
 // ---- checkpoint: the reference has none (state is lost on every experiment switch) ----
 // File = "NBXCKPT1" | int32 n | int32 reserved | 7 arrays of n little-endian f32: px py pz vx vy vz m
 int32_t nbx_save(nbx_engine* e, const char* path)

@@ -505,6 +505,9 @@ int step_bh(nbx_engine* e, float theta, float dt);
 int bh3_refusal(const nbx_engine* e);   // NBX_OK, or the status of a configuration the octree path does not serve (text in nbx_last_error)
 int step_bh3(nbx_engine* e, float theta, float dt);
 int forces_bh3(nbx_engine* e, float theta, float* fx, float* fy, float* fz);
+// K14: phi_i of the Newtonian octree walk (returns n), and nbx_conserved's twelve sums with the potential made from that walk
+int potential_bh3(nbx_engine* e, float theta, int cap, float* phi);
+int conserved_bh3(nbx_engine* e, float theta, int count, double* out);
 int oct_dump(nbx_engine* e, void* rows, int cap);
 int oct_moments(nbx_engine* e, float* rows, int cap);   // one 8-float row per node of oct_dump's order (either law)
 // engine_diag.cpp: the fp64 all-pairs sweep (K7) on the live device state, which it never modifies

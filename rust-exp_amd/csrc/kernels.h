@@ -118,6 +118,12 @@ hipError_t launch_oct_moment_rows(const OctNode* nodes, int n_nodes, int interio
 // when quads != nullptr (monopole only, and no OctQuad read, when it is null)
 hipError_t launch_oct_walk_newton(float4* posm, int n, const unsigned* order, const OctGroup* groups, const OctQuad* quads,
                                   float4* forces, float4* kick_vel, float dt, hipStream_t stream);
+// ---- K14 (bh_oct_potential.hip): the potential of that walk: same records, same opening decisions ----
+// phi_i = sum over the taken children of -M r (+ 0.5 tr(P) r^3 - 1.5 (x^T P x) r^5 for an interior one when quads != nullptr), plus
+// m_i / sqrt(eps) for the body's own leaf: j = i excluded.  Exactly one output: phi[i] (float, body order) or wide[i] = (0, 0, 0,
+// (double)phi_i), the record launch_conserved64 reads
+hipError_t launch_oct_phi(const float4* posm, int n, const unsigned* order, const OctGroup* groups, const OctQuad* quads, float* phi,
+                          double4* wide, hipStream_t stream);
 
 struct ForceLaunch {
     int grid, block, jsplit, bpt, dim, variant;

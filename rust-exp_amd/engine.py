@@ -255,6 +255,10 @@ def lib():
     L.nbx_bh_oct_dump.restype = i32
     L.nbx_bh_oct_moments.argtypes = [E, _f32p, i32]
     L.nbx_bh_oct_moments.restype = i32
+    L.nbx_bh_potential.argtypes = [E, C.c_float, i32, _f32p]
+    L.nbx_bh_potential.restype = i32
+    L.nbx_bh_conserved.argtypes = [E, C.c_float, i32, C.c_void_p]
+    L.nbx_bh_conserved.restype = i32
     L.nbx_set_shard.argtypes = [E, i32, i32]
     L.nbx_set_shard.restype = i32
     L.nbx_get_slab.argtypes = [E, C.POINTER(i32), C.POINTER(i32)]
@@ -550,6 +554,10 @@ class NBodyEngine:
         W = -sum_{i<j} m_i m_j (|d|^2 + eps)^(-1/2) under set_law("newton")."""
         out = np.zeros(max(count, NBX_CONS_COUNT), np.float64)
         _check(self._L.nbx_conserved(self._h, count, _p(out)))
+        return self._conserved_dict(out)
+
+    @staticmethod
+    def _conserved_dict(out):
         return {"kinetic": float(out[NBX_CONS_KINETIC]), "potential": float(out[NBX_CONS_POTENTIAL]),
                 "mass": float(out[NBX_CONS_MASS]), "momentum": out[NBX_CONS_PX:NBX_CONS_PX + 3].copy(),
                 "angular_momentum": out[NBX_CONS_LX:NBX_CONS_LX + 3].copy(), "mass_moment": out[NBX_CONS_MRX:NBX_CONS_MRX + 3].copy()}
@@ -679,6 +687,21 @@ class NBodyEngine:
         rows = np.zeros(max(cnt, 1), dt)
         cnt = _check(self._L.nbx_bh_oct_moments(self._h, rows.ctypes.data_as(_f32p), cnt))
         return rows[:cnt]
+
+    def bh_potential(self, theta):
+        """phi_i of every body from one octree walk under set_law("newton") with set_bh_dim(3) (nbx_bh_potential), float32 in body
+        order: -M r per taken node, + 0.5 tr(P) r^3 - 1.5 (x^T P x) r^5 for an interior one unless set_bh_quadrupole(False);
+        j = i excluded, as in forces_f64's phi.  State untouched."""
+        phi = np.zeros(max(self.num_particles(), 1), np.float32)
+        cnt = _check(self._L.nbx_bh_potential(self._h, theta, len(phi), phi.ctypes.data_as(_f32p)))
+        return phi[:cnt]
+
+    def bh_conserved(self, theta, count=NBX_CONS_COUNT):
+        """conserved()'s dict with "potential" = 1/2 sum m_i phi_i over bh_potential(theta)'s phi (nbx_bh_conserved): one tree walk
+        instead of the all-pairs fp64 sweep; the other entries are conserved()'s bit for bit."""
+        out = np.zeros(max(count, NBX_CONS_COUNT), np.float64)
+        _check(self._L.nbx_bh_conserved(self._h, theta, count, _p(out)))
+        return self._conserved_dict(out)
 
     # sharding
     def set_shard(self, rank, world):
